@@ -20,6 +20,10 @@ Modes:
 
 Run standalone (1 GPU) or under `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N bench.py --gpus N ...`.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON
+result line. --dump-outputs DIR also saves what the last timed step
+delivered; --full adds the p50 round-trip latency measurement.
 """
 
 import argparse
@@ -71,8 +75,17 @@ def parse_args():
                         "fused ZPushPull single-trip round)")
     p.add_argument("--emb-rows", type=int, default=1 << 20)
     p.add_argument("--emb-width", type=int, default=64)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline GB/s does not need: "
+                        "the p50 round-trip latencies (dense, 1 MB & 64 MB)")
     p.add_argument("--rtt-iters", type=int, default=100)
-    p.add_argument("--no-rtt", action="store_true")
+    p.add_argument("--no-rtt", action="store_true",
+                   help="with --full: skip the round-trip latency measurement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the buffers the last "
+                        "step pulled (rank 0's worker) as DIR/<name>.npy, "
+                        "float32; at most 64 MB in all, larger buffers as a "
+                        "fixed seeded sample of their elements")
     p.add_argument("--pool-gb", type=int, default=0, help="0 = auto-size")
     p.add_argument("--smoke", action="store_true", help="tiny correctness run")
     return p.parse_args()
@@ -123,8 +136,34 @@ def reduce_max(values, rank, world):
     return t.tolist()
 
 
+# --dump-outputs budget: 64 MB cap less room for the .npy headers
+DUMP_BUDGET_BYTES = 60 << 20
+DUMP_SAMPLE_SEED = 4321
+
+
+def dump_outputs(dirname, named_bufs, bf16):
+    """Write each received buffer as <dirname>/<name>.npy (float32). The
+    byte budget is split evenly; a buffer over its share is reduced to a
+    seeded choice of element indices, the same for every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(named_bufs)
+    picks = {}
+    for name, buf in named_bufs:
+        a = buf.to_numpy_f32()
+        if bf16:
+            # payload is bf16: widen (exactly) to float32
+            a = (a.view(np.uint16).astype(np.uint32) << 16).view(np.float32)
+        if a.size > share:
+            if a.size not in picks:
+                pick_rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+                picks[a.size] = np.sort(pick_rng.choice(a.size, share, replace=False))
+            a = a[picks[a.size]]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
+    t_start = time.perf_counter()
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", rank))
@@ -186,7 +225,8 @@ def main():
 
     def trace(msg):
         if os.environ.get("XPS_BENCH_TRACE"):
-            print(f"# [rank {rank}] {msg}", file=sys.stderr, flush=True)
+            print(f"# [rank {rank}] +{time.perf_counter() - t_start:.2f}s {msg}",
+                  file=sys.stderr, flush=True)
 
     cluster = Cluster(ps, n, rank, local, device,
                       master if world > 1 else "127.0.0.1", master_port + 137, pool_gb)
@@ -255,6 +295,7 @@ def main():
                 worker.wait(ts)
 
         bytes_per_worker_step = 2.0 * vbytes
+        received = [("pull", pull_buf)]
     else:
         keys_np = np.array(keys, dtype=np.uint64)
         batch = args.batch_keys and args.mode == "dense" and device >= 0
@@ -285,15 +326,23 @@ def main():
             bytes_per_worker_step = 2.0 * total_msg_bytes
             push_bufs, pull_bufs = [], []
             push_ptrs, pull_ptrs = [], []
+            received = [("pull", bpull_r)]
         else:
             push_bufs, pull_bufs = [], []
-            for sz in msg_sizes:
+            # ONE seeded draw serves every key: key j pushes the window
+            # payload[j : j + len] (distinct per key, so a key mix-up shows
+            # in the pulled values). Drawing every key's payload afresh
+            # costs tens of seconds of host RNG for the 8 GiB headline
+            # model (a plain run took 20 s on an MI355X host, 2.5 s now).
+            payload = rng.standard_normal(max(msg_sizes) // 4 + len(msg_sizes)).astype(np.float32)
+            for j, sz in enumerate(msg_sizes):
                 # host buffers come from the shm pool so the CPU config
                 # rides the same-host zero-copy plane (not TCP)
                 b = alloc(sz)
-                b.copy_from(rng.standard_normal(sz // 4).astype(np.float32))
+                b.copy_from(payload[j:j + sz // 4])
                 push_bufs.append(b)
                 pull_bufs.append(alloc(sz))
+            del payload
             push_ptrs = [b.ptr for b in push_bufs]
             pull_ptrs = [b.ptr for b in pull_bufs]
             uniform = len(set(msg_sizes)) == 1
@@ -308,6 +357,9 @@ def main():
                 bpull = [ps.pool_alloc(k * msg_sizes[0]) for _ in range(n)]
                 for b in bpush:
                     b.copy_from(rng.standard_normal(k * msg_sizes[0] // 4).astype(np.float32))
+                received = [(f"pull_server{s:02d}", bpull[s]) for s in range(n)]
+            else:
+                received = [(f"pull_key{j:04d}", b) for j, b in enumerate(pull_bufs)]
 
             def one_step():
                 if batch:
@@ -352,10 +404,15 @@ def main():
     t1 = time.perf_counter()
     ps.barrier("worker", ps.WORKER_GROUP)
     elapsed = t1 - t0
+    trace("timed steps done")
 
-    # p50 round trip: one blocking push+pull of a single key
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, received, args.dtype == "bf16")
+        trace("outputs written")
+
+    # p50 round trip (--full): one blocking push+pull of a single key
     rtts = {}
-    if not args.no_rtt and not args.smoke and args.mode == "dense":
+    if args.full and not args.no_rtt and not args.smoke and args.mode == "dense":
         for j, (sz_name, sz) in enumerate((("1mb", 1 << 20), ("64mb", 64 << 20))):
             if sz > max(msg_sizes):
                 continue
