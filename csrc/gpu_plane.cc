@@ -31,6 +31,12 @@ static const size_t kInlineMax = 4096;  // host blobs above this ride the shm po
 // pointer equality against registered buffers; here the transport
 // itself reports it)
 std::atomic<uint64_t> g_zero_copy_recv{0};
+std::atomic<uint64_t> g_fused_assign{0};
+
+bool FusedAssignEnabled() {
+  static const bool on = Environment::Get()->GetInt("XPS_FUSED_ASSIGN", 1) != 0;
+  return on;
+}
 
 namespace {
 // process-wide dedup of hipIpcOpenMemHandle (two vans of a joint process
@@ -439,6 +445,15 @@ Postoffice* GpuPlane::LocalPeer(Peer* p) {
   return po;
 }
 
+// ack of a one-sided push, or of a one-sided fused push+pull (its
+// response keeps the request's kOptEntryPush; the handler's own fused
+// launch clears it): the handler launched nothing, so there is no event
+// to wait for
+static bool KernelLessAck(const Message& msg) {
+  return !msg.meta.request && msg.meta.push && (msg.meta.option & kOptInPlace) &&
+         (!msg.meta.pull || (msg.meta.option & kOptEntryPush));
+}
+
 // does this (device-vals) pull response REQUIRE the staging path? The
 // worker-side merge expects host bytes unless an in-place HBM
 // destination was advertised.
@@ -600,6 +615,62 @@ bool GpuPlane::LocalPullRead(int peer_id, void* dst, uint64_t entry_off, size_t 
   return true;
 }
 
+bool GpuPlane::EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out) {
+  if (!FusedAssignEnabled()) return false;
+  if (!(msg.meta.option & kOptPullAddr) || (msg.meta.option & kOptHostAddr)) return false;
+  static const bool local_one_sided =
+      Environment::Get()->GetInt("XPS_LOCAL_ONE_SIDED", 0) != 0;
+  // same-process peers stay on the handler's launch lane by default (see
+  // the kOptEntryPush block in Send for the measurement)
+  Postoffice* elpo = LocalPeer(p);
+  GpuPlane* rplane =
+      elpo ? dynamic_cast<GpuPlane*>(elpo->van() ? elpo->van()->plane() : nullptr) : nullptr;
+  bool can = elpo ? (local_one_sided && rplane != nullptr) : EnsureRing(p);
+  if (!can) return false;
+  SArray<char> vals = msg.data[1];
+  size_t len = vals.size();
+  if (len == 0) return false;
+  char* entry = ResolvePeer(p, msg.meta.entry_addr, len);
+  char* dst = static_cast<char*>(HbmPool::Get()->PtrOf(msg.meta.addr, len));
+  if (!entry || !dst || !kern::Disjoint3(entry, dst, vals.data(), len)) return false;
+  XPS_STAGE(entry_push_pull);
+  hipStream_t stream = elpo ? rplane->StreamForPeer(po_->node_id()) : StreamForPeer(p->node.id);
+  XPS_HIP_CHECK(hipSetDevice(device_));
+  kern::DenseAssign2(entry, dst, vals.data(), len, stream);
+  g_fused_assign.fetch_add(1, std::memory_order_relaxed);
+  g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
+  Message meta_msg;
+  meta_msg.meta = msg.meta;
+  meta_msg.meta.option |= kOptInPlace;
+  meta_msg.meta.val_len = static_cast<int64_t>(len);
+  meta_msg.meta.data_type.clear();
+  for (size_t i = 0; i < msg.data.size(); ++i) {
+    if (i == 1 || msg.data[i].on_device()) continue;
+    meta_msg.data.push_back(msg.data[i]);
+    meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
+  }
+  int64_t bytes = 64 + static_cast<int64_t>(len);
+  Message keepalive;
+  keepalive.data.push_back(vals);
+  std::string payload;
+  if (!elpo) {
+    std::vector<char> br(meta_msg.data.size(), 0);
+    XPS_CHECK(Serialize(meta_msg, br, &payload));
+  }
+  hipEvent_t ev = GetEvent();
+  XPS_HIP_CHECK(hipEventRecord(ev, stream));
+  {
+    std::lock_guard<std::mutex> lk(pend_mu_);
+    pending_[p->node.id].push_back(Pending{ev, p->node.id, std::move(payload),
+                                           std::move(meta_msg), std::move(keepalive), bytes,
+                                           elpo});
+  }
+  pending_count_.fetch_add(1);
+  p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
+  *bytes_out = bytes;
+  return true;
+}
+
 void GpuPlane::EnqueueLocal(Message msg, int64_t bytes) {
   {
     std::lock_guard<std::mutex> lk(local_mu_);
@@ -693,8 +764,7 @@ int64_t GpuPlane::SendLocal(Message& msg, Peer* p, Postoffice* lpo) {
 
   // ack of a one-sided push: the handler launched nothing for it — no
   // event to wait, deliver right away
-  bool kernel_less_ack = response && msg.meta.push && !msg.meta.pull &&
-                         (msg.meta.option & kOptInPlace);
+  bool kernel_less_ack = KernelLessAck(msg);
   if (response && device_ >= 0 && !kernel_less_ack) {
     // GPU handler output: deliver once this peer's lane drained
     XPS_STAGE(local_defer);
@@ -802,6 +872,20 @@ int64_t GpuPlane::Send(Message& msg, const Node& peer_node) {
       return bytes;
     }
     msg.meta.option &= ~kOptEntryPush;  // entry unmapped: normal path
+  }
+
+  // ---- one-sided FUSED push+pull: same idea, one dual-write kernel.
+  // kOptInPlace on the caller's msg reports that the write really ran
+  // (KVWorker::Send keeps its one_sided flag honest from it).
+  if (msg.meta.request && msg.meta.push && msg.meta.pull && (msg.meta.option & kOptEntryPush)) {
+    int64_t bytes = 0;
+    if (device_ >= 0 && msg.data.size() > 1 && msg.data[1].on_device() &&
+        EntryPushPull(msg, p, &bytes)) {
+      msg.meta.option |= kOptInPlace;
+      return bytes;
+    }
+    msg.meta.option &= ~kOptEntryPush;  // declined: normal fused request
+    msg.meta.entry_addr = 0;
   }
 
   if (Postoffice* lpo = LocalPeer(p)) return SendLocal(msg, p, lpo);
@@ -919,8 +1003,7 @@ int64_t GpuPlane::Send(Message& msg, const Node& peer_node) {
   }
   int64_t bytes = static_cast<int64_t>(payload.size()) + ref_bytes;
   // ack of a one-sided push: the handler launched nothing — no event
-  bool kernel_less_ack = response && msg.meta.push && !msg.meta.pull &&
-                         (msg.meta.option & kOptInPlace);
+  bool kernel_less_ack = KernelLessAck(msg);
   if (response && device_ >= 0 && !kernel_less_ack) {
     // order behind any handler kernels on this peer's lane (the handler
     // flags pull-lane work via kOptPullLane; everything else is lane 0).

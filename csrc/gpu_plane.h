@@ -33,6 +33,13 @@ namespace xps {
 // zero-copy reception counter (by-ref blobs resolved straight into a
 // mapped peer pool; see gpu_plane.cc)
 extern std::atomic<uint64_t> g_zero_copy_recv;
+// fused dual-write launches (kern::DenseAssign2) in this process: the
+// dense handler's fused push+pull fast path plus the worker's one-sided
+// GpuPlane::EntryPushPull
+extern std::atomic<uint64_t> g_fused_assign;
+// XPS_FUSED_ASSIGN (default 1): 0 restores the two-kernel push-then-pull
+// everywhere (A/B runs within one build)
+bool FusedAssignEnabled();
 
 class Postoffice;
 
@@ -145,6 +152,14 @@ class GpuPlane : public DataPlane {
   void RingPollLoop();
   void CompletionLoop();
   hipStream_t StreamLane(int node_id, int lane);
+  // One-sided fused push+pull (request carries kOptEntryPush with the
+  // cached entry offset in meta.entry_addr and our own pull destination
+  // in meta.addr): ONE dual-write kernel of ours stores vals to the
+  // peer's mapped store entry and to the local destination, then the
+  // meta-only kOptInPlace notification follows the completion event.
+  // Returns false — nothing launched, nothing queued — when the entry or
+  // the destination cannot be resolved or the peer has no ring.
+  bool EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out);
   void DeferSendInternal(Peer* p, int peer_id, hipStream_t stream, Message resend,
                          Message keepalive, std::string payload, int64_t bytes);
 

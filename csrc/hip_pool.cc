@@ -181,6 +181,17 @@ bool HbmPool::OffsetOf(const void* p, uint64_t* global_off) const {
   return false;
 }
 
+void* HbmPool::PtrOf(uint64_t global_off, uint64_t len) const {
+  for (auto& slab : slabs_) {
+    if (!slab.exported) continue;
+    if (global_off >= slab.global_begin && global_off - slab.global_begin <= slab.capacity &&
+        len <= slab.capacity - (global_off - slab.global_begin)) {
+      return static_cast<char*>(slab.base) + (global_off - slab.global_begin);
+    }
+  }
+  return nullptr;
+}
+
 SArray<char> HbmPool::AllocArray(size_t nbytes) {
   char* p = static_cast<char*>(Alloc(nbytes));
   return SArray<char>(p, nbytes, [](char* q) { HbmPool::Get()->Free(q); }, device_);

@@ -48,6 +48,9 @@ class HbmPool {
   void Free(void* p);
   // true iff p lies inside the pool; fills the GLOBAL byte offset
   bool OffsetOf(const void* p, uint64_t* global_off) const;
+  // inverse of OffsetOf: the local pointer of [global_off, global_off +
+  // len), or nullptr when the range is not inside one exported slab
+  void* PtrOf(uint64_t global_off, uint64_t len) const;
 
   // SArray drawing from the pool (freed back on last release)
   SArray<char> AllocArray(size_t nbytes);

@@ -16,6 +16,21 @@ namespace kern {
 
 // dst[i] = src[i] (bytes; 16B-vectorized grid-stride copy kernel)
 void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s);
+// dst0[i] = dst1[i] = src[i] (bytes; one 16 B load, two 16 B stores per
+// lane — the fused push+pull of one key). The three ranges must be
+// pairwise disjoint. grid_cap > 0 caps the grid (tests use it to force
+// many grid-stride iterations on a small buffer).
+void DenseAssign2(void* dst0, void* dst1, const void* src, size_t nbytes, hipStream_t s,
+                  int grid_cap = 0);
+// true iff the three len-byte ranges are pairwise disjoint (DenseAssign2's
+// precondition; callers check it before choosing the fused kernel)
+inline bool Disjoint3(const void* a, const void* b, const void* c, size_t len) {
+  auto apart = [len](const void* x, const void* y) {
+    uintptr_t p = reinterpret_cast<uintptr_t>(x), q = reinterpret_cast<uintptr_t>(y);
+    return p + len <= q || q + len <= p;
+  };
+  return apart(a, b) && apart(a, c) && apart(b, c);
+}
 // dst[i] += src[i] (fp32)
 void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s);
 // dst[i] += src[i] (bf16 payloads, fp32 accumulate in-register,

@@ -28,8 +28,8 @@ inline int GridFor(size_t work_items, int cap = 8192) {
 }
 
 // NOTE: nontemporal loads/stores were measured 3 % SLOWER end-to-end
-// here — the 256 MiB Infinity Cache serves the overlapped pull's re-read
-// of the just-written store, and nt stores bypass it. Keep plain float4.
+// here — the 256 MiB Infinity Cache serves a following pull's re-read of
+// the just-written store, and nt stores bypass it. Keep plain float4.
 __global__ void assign_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n4) {
   size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
@@ -40,6 +40,39 @@ __global__ void assign_tail_kernel(char* __restrict__ dst, const char* __restric
                                    size_t begin, size_t end) {
   size_t i = begin + blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
   if (i < end) dst[i] = src[i];
+}
+
+// Fused push+pull of one key: one 16 B load per lane per iteration, two
+// 16 B stores (store entry + the requester's pull destination). Moves
+// 3 bytes of traffic per payload byte where the assign_kernel pair moved
+// 4, in one launch. The three ranges must be pairwise disjoint. The
+// sub-16 B tail [tail_begin, nbytes) rides the same launch as a byte
+// grid-stride loop; launched with n4 == 0 and tail_begin == 0 that loop
+// copies a whole (misaligned) range.
+// Plain stores, no unrolling — same-session A/B on the 128 x 64 MiB
+// headline, 3 alternating runs each (profiles/dense64_fused_rocprof.md):
+// this kernel 3283-3428 GB/s; nontemporal store to the store entry (no
+// longer re-read by this round's pull) 3327-3397, inside that spread, so
+// not adopted; 2 loads in flight per lane 3026-3069 and 2 loads + nt
+// 3226-3244, both slower; 4 loads in flight 3294-3401, no gain.
+__global__ void assign2_kernel(uint4* __restrict__ dst0, uint4* __restrict__ dst1,
+                               const uint4* __restrict__ src, size_t n4, size_t tail_begin,
+                               size_t nbytes) {
+  size_t tid = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    uint4 v = src[i];
+    dst0[i] = v;
+    dst1[i] = v;
+  }
+  char* b0 = reinterpret_cast<char*>(dst0);
+  char* b1 = reinterpret_cast<char*>(dst1);
+  const char* bs = reinterpret_cast<const char*>(src);
+  for (size_t i = tail_begin + tid; i < nbytes; i += stride) {
+    char c = bs[i];
+    b0[i] = c;
+    b1[i] = c;
+  }
 }
 
 __global__ void sum_kernel_f32(float4* __restrict__ dst, const float4* __restrict__ src,
@@ -416,6 +449,21 @@ void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s) {
     hipLaunchKernelGGL(assign_tail_kernel, dim3(1), dim3(kBlock), 0, s, static_cast<char*>(dst),
                        static_cast<const char*>(src), n4 * 16, nbytes);
   }
+}
+
+void DenseAssign2(void* dst0, void* dst1, const void* src, size_t nbytes, hipStream_t s,
+                  int grid_cap) {
+  if (nbytes == 0) return;
+  // the 16 B path needs all three pointers 16 B-aligned (pool buffers
+  // are); anything else takes the byte loop for the whole range
+  bool aligned = ((reinterpret_cast<uintptr_t>(dst0) | reinterpret_cast<uintptr_t>(dst1) |
+                   reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+  size_t n4 = aligned ? nbytes / 16 : 0;
+  int grid = GridFor(n4 ? n4 : nbytes);
+  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
+  hipLaunchKernelGGL(assign2_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<uint4*>(dst0),
+                     static_cast<uint4*>(dst1), static_cast<const uint4*>(src), n4, n4 * 16,
+                     nbytes);
 }
 
 void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s) {

@@ -55,6 +55,7 @@ struct KVMeta {
   int customer_id = 0;
   Key key = 0;          // fast-path single key
   uint64_t addr = 0;    // pull: requester's destination pool offset
+  uint64_t entry_addr = 0;  // fused push+pull: store-entry offset (see Meta)
   int64_t val_len = 0;
   int option = 0;
   int src_dev = kCPU;
@@ -148,6 +149,22 @@ class KVWorker : public SimpleApp {
   }
 
   void Wait(int timestamp) { obj_->WaitRequest(timestamp); }
+
+  // true when a live advert of exactly `nbytes` exists for the key's
+  // server: learned from a push ACK or a fused response of an assign-mode
+  // GPU dense handler, and still pinned to that server process's uid
+  bool HasEntry(const Key& key, size_t nbytes) {
+    // same key -> server mapping as DefaultSlicer (lower bound on begins)
+    const auto& ranges = po_->GetServerKeyRanges();
+    size_t i = 0;
+    while (i + 1 < ranges.size() && key >= ranges[i + 1].begin) ++i;
+    if (ranges.empty()) return false;
+    int sid = ServerRankToID(static_cast<int>(i));
+    std::lock_guard<std::mutex> lk(mu_);
+    const EntryRec* rec = FindEntryLocked(sid, key);
+    return rec && rec->len == static_cast<int64_t>(nbytes) &&
+           po_->van()->GetNode(sid).shm_uid == rec->uid;
+  }
 
   void set_slicer(Slicer s) { slicer_ = std::move(s); }
 
@@ -304,6 +321,22 @@ class KVWorker : public SimpleApp {
             msg.meta.addr = off;
             msg.meta.option |= kOptPullAddr | kOptHostAddr;
           }
+          // one-sided fused round: a cached advert of exactly this
+          // length lets OUR dual-write kernel store vals into the
+          // server's entry and into dst at once (GpuPlane::EntryPushPull).
+          // Same-process peers keep the handler's launch lane unless
+          // XPS_LOCAL_ONE_SIDED=1 (the plane decides; it declines by
+          // stripping the option).
+          if (s.keys.size() == 1 && cmd != kCmdSum && s.vals.on_device() &&
+              dst->on_device() && (msg.meta.option & kOptPullAddr) && FusedAssignEnabled()) {
+            std::lock_guard<std::mutex> lk(mu_);
+            const EntryRec* rec = FindEntryLocked(msg.meta.recver, s.keys[0]);
+            if (rec && rec->len == static_cast<int64_t>(s.vals.nbytes()) &&
+                po_->van()->GetNode(msg.meta.recver).shm_uid == rec->uid) {
+              msg.meta.entry_addr = rec->off;
+              msg.meta.option |= kOptEntryPush;
+            }
+          }
         }
       } else {
         // One-sided pull (RDMA_READ analog, assign-mode steady state):
@@ -370,6 +403,18 @@ class KVWorker : public SimpleApp {
         if (!s.lens.empty()) msg.AddData(s.lens);
       }
       po_->van()->Send(msg);
+      if (push && pull && s.keys.size() == 1) {
+        // the plane marks the request kOptInPlace only when it really ran
+        // the one-sided dual write; a fused request applied by the server
+        // (or sent over TCP) leaves the key's one-sided chain broken
+        bool did = (msg.meta.option & kOptEntryPush) && (msg.meta.option & kOptInPlace);
+        std::lock_guard<std::mutex> lk(mu_);
+        auto nit = entry_cache_.find(msg.meta.recver);
+        if (nit != entry_cache_.end()) {
+          auto it = nit->second.find(s.keys[0]);
+          if (it != nit->second.end()) it->second.one_sided = did;
+        }
+      }
       (void)val_elem_off;
     }
   }
@@ -393,6 +438,11 @@ class KVWorker : public SimpleApp {
     {
       std::lock_guard<std::mutex> lk(mu_);
       if (msg.meta.pull) {
+        // a fused push+pull response advertises the entry too (offset in
+        // entry_addr: addr still names the in-place destination)
+        if (msg.meta.push && (msg.meta.option & kOptEntryAddr)) {
+          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.entry_addr, msg.meta.val_len);
+        }
         auto& got = recv_kvs_[ts];
         got.push_back(RecvSlice{kvs, msg.meta.option, msg.meta.val_len});
         last = static_cast<int>(got.size()) >= expected_[ts];
@@ -400,9 +450,7 @@ class KVWorker : public SimpleApp {
         // a push ACK may advertise the server's entry offset for this
         // key: cache it so later assign pushes go one-sided
         if (msg.meta.option & kOptEntryAddr) {
-          entry_cache_[msg.meta.sender][msg.meta.key] =
-              EntryRec{msg.meta.addr, msg.meta.val_len,
-                       po_->van()->GetNode(msg.meta.sender).shm_uid};
+          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.addr, msg.meta.val_len);
         }
         int n = ++push_acks_[ts];
         last = n >= expected_[ts];
@@ -519,6 +567,19 @@ class KVWorker : public SimpleApp {
   };
   std::unordered_map<int, std::unordered_map<Key, EntryRec>> entry_cache_;
 
+  // (re)learn an advert: the server applied this request itself, so the
+  // key's one-sided chain restarts (one_sided = false)
+  void CacheEntryLocked(int server_id, Key key, uint64_t off, int64_t len) {
+    entry_cache_[server_id][key] = EntryRec{off, len, po_->van()->GetNode(server_id).shm_uid};
+  }
+
+  const EntryRec* FindEntryLocked(int server_id, Key key) const {
+    auto nit = entry_cache_.find(server_id);
+    if (nit == entry_cache_.end()) return nullptr;
+    auto it = nit->second.find(key);
+    return it == nit->second.end() ? nullptr : &it->second;
+  }
+
   Slicer slicer_;
   std::mutex mu_;
   std::unordered_map<int, Callback> callbacks_;
@@ -560,6 +621,7 @@ class KVServer : public SimpleApp {
     msg.meta.recver = req.sender;
     msg.meta.key = req.key;
     msg.meta.addr = req.addr;         // in-place pull destination (pool offset)
+    msg.meta.entry_addr = req.entry_addr;
     msg.meta.option = req.option;
     msg.meta.val_len = req.val_len;   // in-place responses keep the request's byte count
     msg.meta.src_dev = res.vals.device();
@@ -588,6 +650,7 @@ class KVServer : public SimpleApp {
     meta.customer_id = msg.meta.customer_id;
     meta.key = msg.meta.key;
     meta.addr = msg.meta.addr;
+    meta.entry_addr = msg.meta.entry_addr;
     meta.val_len = msg.meta.val_len;
     meta.option = msg.meta.option;
     meta.src_dev = msg.meta.src_dev;

@@ -84,10 +84,14 @@ static const int kOptHostAddr = 8;  // meta.addr is a HOST-shm-pool offset (else
 static const int kOptPullLane = 16;
 // push ACK: meta.addr/val_len advertise the server's store-entry pool
 // offset for this key — the worker may write subsequent assign pushes
-// there ONE-SIDED (the rdma_van push_addr_ steady state, :486-508)
+// there ONE-SIDED (the rdma_van push_addr_ steady state, :486-508).
+// A fused push+pull response carries the offset in meta.entry_addr.
 static const int kOptEntryAddr = 32;
 // push REQUEST: the sender has a cached entry offset in meta.addr and
-// asks the plane to write vals there itself + deliver the meta only
+// asks the plane to write vals there itself + deliver the meta only.
+// On a fused push+pull request the offset is in meta.entry_addr and the
+// plane writes vals to BOTH the entry and the sender's own pull
+// destination in one kernel (GpuPlane::EntryPushPull).
 static const int kOptEntryPush = 64;
 
 enum DataType : int { kChar = 0, kInt32, kInt64, kUint64, kFloat32, kFloat64, kUint8 };
@@ -115,6 +119,10 @@ struct Meta {
   // fast-path fields (single-key messages; mirrors ps-lite meta.key/addr/val_len/option)
   Key key = 0;
   uint64_t addr = 0;           // pull: requester's destination pool offset
+  // fused push+pull RESPONSE: meta.addr keeps the in-place destination,
+  // so the store-entry advert (kOptEntryAddr) rides here instead; the
+  // advertised length is val_len, as for a push ACK
+  uint64_t entry_addr = 0;
   int64_t val_len = 0;         // vals bytes
   int option = 0;
   uint64_t msg_sig = 0;        // resender signature (0 = none)

@@ -148,7 +148,11 @@ class PyKVWorker {
   }
 
   // rn50/mixed-size fast path: per key, push (and optionally the pull
-  // right behind it — per-peer ordering makes that safe), then wait all
+  // right behind it — per-peer ordering makes that safe), then wait all.
+  // An overlapped pair whose key has a live entry advert (only an assign-
+  // mode GPU dense handler advertises) goes out as ONE fused ZPushPull:
+  // one dual-write kernel instead of a push kernel + a pull kernel. The
+  // first step of a run has no adverts yet and uses the plain pair.
   void RoundMixed(py::array_t<uint64_t> keys, const std::vector<uintptr_t>& push_ptrs,
                   const std::vector<uintptr_t>& pull_ptrs, const std::vector<size_t>& sizes,
                   int device, int cmd, bool overlap) {
@@ -171,6 +175,13 @@ class PyKVWorker {
       SArray<int> lens(1);
       lens[0] = static_cast<int>(n);
       SArray<float> v(reinterpret_cast<float*>(push_ptrs[i]), n, device);
+      if (overlap && !pull_ptrs.empty() && device >= 0 && cmd != kCmdSum &&
+          push_ptrs[i] != pull_ptrs[i] && FusedAssignEnabled() &&
+          w_.HasEntry(keys.data()[i], sizes[i])) {
+        dsts.emplace_back(new SArray<float>(reinterpret_cast<float*>(pull_ptrs[i]), n, device));
+        tss.push_back(w_.ZPushPull(karrs[i], v, dsts.back().get(), lens, cmd));
+        continue;
+      }
       tss.push_back(w_.ZPush(karrs[i], v, lens, cmd));
       if (overlap && !pull_ptrs.empty()) tss.push_back(issue_pull(i));
     }
@@ -561,6 +572,8 @@ PYBIND11_MODULE(_core, m) {
   // transport-level zero-copy assertion (reference parity:
   // test_benchmark.cc:169-181 registered-buffer pointer equality)
   m.def("zero_copy_recv_count", []() { return g_zero_copy_recv.load(); });
+  // fused dual-write launches (server fast path + worker one-sided path)
+  m.def("fused_assign_count", []() { return g_fused_assign.load(); });
 
   // per-peer plane traffic: {node_id: (tx_bytes, rx_bytes)} — each peer
   // pair rides its own xGMI link, so this is the per-link utilization
@@ -809,6 +822,14 @@ PYBIND11_MODULE(_core, m) {
     kern::DenseAssign(reinterpret_cast<void*>(dst), reinterpret_cast<void*>(src), nbytes, nullptr);
     gpu::DeviceSync(-1);
   });
+  m.def("k_dense_assign2",
+        [](uintptr_t dst0, uintptr_t dst1, uintptr_t src, size_t nbytes, int grid_cap) {
+          kern::DenseAssign2(reinterpret_cast<void*>(dst0), reinterpret_cast<void*>(dst1),
+                             reinterpret_cast<void*>(src), nbytes, nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("dst0"), py::arg("dst1"), py::arg("src"), py::arg("nbytes"),
+        py::arg("grid_cap") = 0);
   m.def("k_dense_sum_f32", [](uintptr_t dst, uintptr_t src, size_t n) {
     kern::DenseSumF32(reinterpret_cast<float*>(dst), reinterpret_cast<float*>(src), n, nullptr);
     gpu::DeviceSync(-1);

@@ -115,6 +115,15 @@ void GpuDenseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
     // pulls for round accounting and cannot fuse them into one message.
     XPS_CHECK(mode_ != DenseMode::kReduce)
         << "ZPushPull is not supported in reduce mode (pulls are held per round)";
+    if (req.option & kOptInPlace) {
+      // one-sided fused round: the worker's dual-write kernel already
+      // stored vals into our entry AND its own destination (the
+      // notification is ordered after that kernel's completion event);
+      // nothing to launch — answer meta-only, in place
+      server->Response(req);
+      return;
+    }
+    if (TryFusedAssign(req, kvs, server)) return;
     HandlePush(req, kvs, server, /*respond=*/false);
     HandlePull(req, kvs, server);
     return;
@@ -126,6 +135,65 @@ void GpuDenseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
   } else {
     server->Response(req);
   }
+}
+
+// Fused push+pull of ONE key in ONE launch: store[key] = dst = src with
+// the dual-write kernel, instead of the push kernel plus the pull kernel
+// that re-read the 'just written' entry. Returns false (nothing done) when
+// any precondition fails; the caller then runs the two-step path.
+bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kvs,
+                                     KVServer<float>* server) {
+  if (!FusedAssignEnabled()) return false;
+  if (mode_ != DenseMode::kAssign || req.cmd == kCmdSum) return false;
+  if (kvs.keys.size() != 1 || !kvs.vals.on_device()) return false;
+  if (!(req.option & kOptPullAddr) || (req.option & kOptHostAddr)) return false;
+  size_t len = kvs.lens.empty() ? kvs.vals.nbytes()
+                                : static_cast<size_t>(kvs.lens[0]) * sizeof(float);
+  if (len == 0 || len != kvs.vals.nbytes() || static_cast<int64_t>(len) != req.val_len) {
+    return false;
+  }
+  auto* plane = ThePlane(po_);
+  if (!plane) return false;
+  char* dst = plane->PeerDst(req.sender, req.addr, len);
+  if (!dst) return false;
+  XPS_STAGE(dense_fused_assign);
+  XPS_HIP_CHECK(hipSetDevice(HbmPool::Get()->device()));
+  Entry* e;
+  {
+    // allocate / retire / zero / grow exactly as HandlePush does
+    std::lock_guard<std::mutex> lk(mu_);
+    e = &store_[kvs.keys[0]];
+    if (e->buf.size() < len) {
+      if (!e->buf.empty()) e->retired.push_back(e->buf);
+      e->buf = HbmPool::Get()->AllocArray(len);
+      XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
+    }
+  }
+  // a LARGER entry keeps its tail: the pull would return more than was
+  // pushed — that is the two-step path's business
+  if (e->buf.size() != len) return false;
+  const char* src = reinterpret_cast<const char*>(kvs.vals.data());
+  if (!kern::Disjoint3(e->buf.data(), dst, src, len)) return false;
+  hipStream_t stream = Stream(req.sender);
+  OrderAfter(e, stream);
+  kern::DenseAssign2(e->buf.data(), dst, src, len, stream);
+  g_fused_assign.fetch_add(1, std::memory_order_relaxed);
+  g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
+  if (NeedChain(req.sender)) e->last_ev = MakeEventRef(po_, stream);
+  // meta-only in-place response; the work ran on the PUSH lane, so no
+  // kOptPullLane — the plane defers delivery on that lane's event. The
+  // entry advert rides along so the worker can go one-sided next time.
+  KVMeta r = req;
+  r.option |= kOptInPlace;
+  r.option &= ~(kOptPullLane | kOptEntryPush);
+  r.val_len = static_cast<int64_t>(len);
+  uint64_t eoff = 0;
+  if (HbmPool::Get()->OffsetOf(e->buf.data(), &eoff)) {
+    r.entry_addr = eoff;
+    r.option |= kOptEntryAddr;
+  }
+  server->Response(r);
+  return true;
 }
 
 GpuDenseHandler::Group* GpuDenseHandler::GroupFor(const SArray<Key>& keys) {

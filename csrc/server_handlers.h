@@ -106,6 +106,9 @@ class GpuDenseHandler {
 
   void HandlePush(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server,
                   bool respond = true);
+  // fused push+pull of one key in one dual-write launch (assign mode);
+  // false = preconditions not met, nothing done
+  bool TryFusedAssign(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void HandleReducePush(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void HandlePull(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void RespondPull(const KVMeta& req, Group* g, KVServer<float>* server);

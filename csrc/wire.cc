@@ -2,7 +2,7 @@
 
 namespace xps {
 
-static const uint8_t kWireVersion = 2;
+static const uint8_t kWireVersion = 3;
 
 static void PackNode(const Node& n, ByteWriter* w) {
   w->I32(n.role);
@@ -58,6 +58,7 @@ void PackMeta(const Meta& m, std::string* out) {
   w.Str(m.body);
   w.U64(m.key);
   w.U64(m.addr);
+  w.U64(m.entry_addr);
   w.I64(m.val_len);
   w.I32(m.option);
   w.U64(m.msg_sig);
@@ -96,6 +97,7 @@ void UnpackMeta(const char* buf, size_t len, Meta* m) {
   m->body = r.Str();
   m->key = r.U64();
   m->addr = r.U64();
+  m->entry_addr = r.U64();
   m->val_len = r.I64();
   m->option = r.I32();
   m->msg_sig = r.U64();
