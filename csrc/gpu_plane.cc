@@ -38,7 +38,35 @@ bool FusedAssignEnabled() {
   return on;
 }
 
+std::atomic<uint64_t> g_fused_launches{0};
+
+bool CoalesceEnabled() {
+  static const bool on = Environment::Get()->GetInt("XPS_COALESCE", 1) != 0;
+  return on;
+}
+
 namespace {
+// CoalesceAppend's hand-over to the deferred response that the same
+// thread sends next (handler -> KVServer::Response -> Send)
+struct CoTicket {
+  const void* plane = nullptr;
+  int peer = 0;
+  std::shared_ptr<void> cev;
+};
+thread_local CoTicket t_co_ticket;
+
+int64_t NowUs() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return static_cast<int64_t>(ts.tv_sec) * 1000000 + ts.tv_nsec / 1000;
+}
+// XPS_COALESCE_HOLD: the completion thread launches a held batch once no
+// key joined it for this long (a burst appends every few microseconds)
+const int64_t kHoldQuietUs = 2000;
+// in-flight payload below which a stream does not count as busy: about
+// 8 us of dual-write traffic at the 5.8 TB/s the kernel sustains
+const size_t kCoBusyBytes = 16u << 20;
+
 // process-wide dedup of hipIpcOpenMemHandle (two vans of a joint process
 // and multiple planes share peer pool mappings; never closed — pools are
 // process-lifetime)
@@ -97,6 +125,9 @@ GpuPlane::GpuPlane(Postoffice* po, int device) : po_(po), device_(device) {
   lanes_ = Environment::Get()->GetInt("XPS_STREAMS_PER_PEER", 2);
   if (lanes_ < 1) lanes_ = 1;
   if (lanes_ > 2) lanes_ = 2;
+  co_hold_ = Environment::Get()->GetInt("XPS_COALESCE_HOLD", 0) != 0;
+  int cap_mb = Environment::Get()->GetInt("XPS_COALESCE_CAP_MB", 1024);
+  co_byte_cap_ = static_cast<size_t>(cap_mb < 1 ? 1 : cap_mb) << 20;
 }
 
 GpuPlane::~GpuPlane() { Stop(); }
@@ -149,11 +180,41 @@ void GpuPlane::Stop() {
     for (auto& lm : local_q_) po_->van()->Deliver(std::move(lm.first));
     local_q_.clear();
   }
+  // launch whatever the coalescer still holds, then drop its event refs
+  // (they return to the event pool, which goes below)
+  if (device_ >= 0) {
+    std::vector<Peer*> all;
+    {
+      std::shared_lock<std::shared_timed_mutex> lk(peers_mu_);
+      for (auto& kv : peers_) all.push_back(kv.second.get());
+    }
+    for (Peer* peer : all) {
+      CoFlush(peer);
+      std::lock_guard<std::mutex> lk(peer->co.mu);
+      peer->co.inflight.clear();
+    }
+  }
   // drain pending sends synchronously so responses are not lost on stop
   {
     std::lock_guard<std::mutex> lk(pend_mu_);
     for (auto& kv : pending_) {
       for (auto& p : kv.second) {
+        if (p.cev) {
+          // shared event of a coalesced launch: wait, never destroy here
+          // (its siblings still hold it; the last one pools it)
+          (void)hipEventSynchronize(p.cev->ev.load(std::memory_order_acquire));
+          if (p.local_po) {
+            DeliverLocal(p.local_po, p.resend, p.bytes);
+          } else {
+            Peer* peer = GetPeer(p.peer_id);
+            auto ring = peer ? RingOf(peer) : nullptr;
+            if (!ring || !ring->Push(p.payload.data(),
+                                     static_cast<uint32_t>(p.payload.size()))) {
+              (void)po_->van()->SendOverTcp(p.resend, p.peer_id);
+            }
+          }
+          continue;
+        }
         (void)hipEventSynchronize(p.ev);
         if (p.local_po) {
           DeliverLocal(p.local_po, p.resend, p.bytes);
@@ -380,6 +441,134 @@ char* GpuPlane::ResolvePeer(Peer* p, uint64_t global_off, uint64_t len) {
 hipStream_t GpuPlane::StreamLane(int node_id, int lane) {
   if (lane >= lanes_) lane = lanes_ - 1;
   Peer* p = GetPeer(node_id);
+  if (lane == 0) CoFlush(p);
+  return RawLane(p, lane);
+}
+
+bool GpuPlane::LanesSplit(int node_id) {
+  return lanes_ >= 2 && GetPeer(node_id)->node.dev_id != device_;
+}
+
+// ---- dual-write launch coalescer ------------------------------------------
+
+void GpuPlane::CoLaunchLocked(Peer* p) {
+  Coalescer& co = p->co;
+  if (co.n == 0) return;
+  hipStream_t stream = RawLane(p, 0);
+  XPS_HIP_CHECK(hipSetDevice(device_));
+  if (co.n == 1) {
+    const kern::Seg2& s = co.segs[0];
+    kern::DenseAssign2(s.dst0, s.dst1, s.src, s.nbytes, stream);
+  } else {
+    kern::BatchedAssign2(co.segs, co.n, stream);
+  }
+  g_fused_launches.fetch_add(1, std::memory_order_relaxed);
+  hipEvent_t ev = GetEvent();
+  XPS_HIP_CHECK(hipEventRecord(ev, stream));
+  co.open->bytes = co.bytes;
+  co.open->ev.store(ev, std::memory_order_release);
+  co.inflight.push_back(std::move(co.open));
+  co.open.reset();
+  co.n = 0;
+  co.bytes = 0;
+  co.n_open.store(0, std::memory_order_release);
+}
+
+// Is the GPU the bottleneck of this stream? Two coalesced launches still
+// in flight AND enough bytes in them to outlast a launch: 2 x 1 MiB drain
+// in about a microsecond, so holding small keys back only adds a hop
+// (measured on the 1 MiB per-key config, see the profile file).
+bool GpuPlane::CoBusyLocked(Peer* p) {
+  CoPruneLocked(p);
+  size_t bytes = 0;
+  for (auto& f : p->co.inflight) bytes += f->bytes;
+  return p->co.inflight.size() >= 2 && bytes >= kCoBusyBytes;
+}
+
+void GpuPlane::CoPruneLocked(Peer* p) {
+  auto& fl = p->co.inflight;
+  while (!fl.empty()) {
+    CoEvent* f = fl.front().get();
+    if (!f->done.load(std::memory_order_acquire) &&
+        hipEventQuery(f->ev.load(std::memory_order_acquire)) != hipSuccess) {
+      break;
+    }
+    fl.pop_front();
+  }
+}
+
+void GpuPlane::CoFlush(Peer* p) {
+  if (p->co.n_open.load(std::memory_order_acquire) == 0) return;
+  std::lock_guard<std::mutex> lk(p->co.mu);
+  CoLaunchLocked(p);
+}
+
+std::shared_ptr<GpuPlane::CoEvent> GpuPlane::CoAppend(Peer* p, const kern::Seg2& seg) {
+  if (!CoalesceEnabled()) return nullptr;
+  Coalescer& co = p->co;
+  std::lock_guard<std::mutex> lk(co.mu);
+  kern::Admit a = kern::CoalesceAdmit(co.segs, co.n, seg);
+  if (a != kern::Admit::kAdmit) CoLaunchLocked(p);
+  if (a == kern::Admit::kReject) return nullptr;
+  if (!co.open) co.open = std::make_shared<CoEvent>(this);
+  std::shared_ptr<CoEvent> cev = co.open;
+  co.segs[co.n++] = seg;
+  co.bytes += seg.nbytes;
+  co.n_open.store(co.n, std::memory_order_release);
+  if (co.n >= kern::kMaxBatch || co.bytes >= co_byte_cap_) {
+    CoLaunchLocked(p);
+  } else if (co_hold_) {
+    co.last_append_us = NowUs();
+  } else {
+    // an idle GPU gets the key at once; a busy one keeps exactly one
+    // launch queued behind the running one and lets the rest pile up
+    if (!CoBusyLocked(p)) CoLaunchLocked(p);
+  }
+  return cev;
+}
+
+bool GpuPlane::CoFrontUnlaunched(Peer* p, const std::shared_ptr<CoEvent>& cev) {
+  Coalescer& co = p->co;
+  std::lock_guard<std::mutex> lk(co.mu);
+  if (co.open != cev) return true;  // launched meanwhile
+  if (co_hold_ && NowUs() - co.last_append_us < kHoldQuietUs) return false;
+  CoLaunchLocked(p);
+  return true;
+}
+
+void GpuPlane::CoRetired(Peer* p) {
+  Coalescer& co = p->co;
+  std::lock_guard<std::mutex> lk(co.mu);
+  bool busy = CoBusyLocked(p);
+  if (!co_hold_ && !busy) CoLaunchLocked(p);
+}
+
+bool GpuPlane::CoalesceAppend(int peer_id, const kern::Seg2& seg) {
+  if (device_ < 0) return false;
+  std::shared_ptr<CoEvent> cev = CoAppend(GetPeer(peer_id), seg);
+  if (!cev) return false;
+  t_co_ticket.plane = this;
+  t_co_ticket.peer = peer_id;
+  t_co_ticket.cev = std::move(cev);
+  return true;
+}
+
+std::shared_ptr<GpuPlane::CoEvent> GpuPlane::TakeTicket(int peer_id) {
+  if (!t_co_ticket.cev || t_co_ticket.plane != this || t_co_ticket.peer != peer_id) {
+    return nullptr;
+  }
+  auto cev = std::static_pointer_cast<CoEvent>(t_co_ticket.cev);
+  t_co_ticket.cev.reset();
+  return cev;
+}
+
+void GpuPlane::CoalesceEnd(int peer_id) {
+  if (!t_co_ticket.cev) return;  // a deferred response took the batch's event
+  t_co_ticket.cev.reset();
+  CoFlush(GetPeer(peer_id));
+}
+
+hipStream_t GpuPlane::RawLane(Peer* p, int lane) {
   hipStream_t s = p->streams[lane].load(std::memory_order_acquire);
   if (s) return s;
   std::lock_guard<std::mutex> lk(p->mu);
@@ -402,6 +591,7 @@ hipStream_t GpuPlane::PullStreamForPeer(int node_id) {
   // 64 MB same-GPU config) — collapse to lane 0.
   Peer* p = GetPeer(node_id);
   if (lanes_ < 2 || p->node.dev_id == device_) return StreamLane(node_id, 0);
+  CoFlush(p);  // pull-lane work is chained behind lane 0 by events recorded there
   return StreamLane(node_id, 1);
 }
 
@@ -634,9 +824,24 @@ bool GpuPlane::EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out) {
   char* dst = static_cast<char*>(HbmPool::Get()->PtrOf(msg.meta.addr, len));
   if (!entry || !dst || !kern::Disjoint3(entry, dst, vals.data(), len)) return false;
   XPS_STAGE(entry_push_pull);
-  hipStream_t stream = elpo ? rplane->StreamForPeer(po_->node_id()) : StreamForPeer(p->node.id);
-  XPS_HIP_CHECK(hipSetDevice(device_));
-  kern::DenseAssign2(entry, dst, vals.data(), len, stream);
+  // queued behind a busy GPU the key joins the open batch of this peer's
+  // lane 0 and shares its launch and event. A same-process peer's write
+  // runs on the RECEIVER plane's stream, whose completions this plane's
+  // queue does not see: it keeps its own launch.
+  std::shared_ptr<CoEvent> cev;
+  // off by default for this site: with two processes on one GPU the
+  // batches of four streams run side by side and the config turned
+  // bimodal (2816-3929 GB/s against the parent's 3078-3242)
+  static const bool co_one_sided =
+      Environment::Get()->GetInt("XPS_COALESCE_ONE_SIDED", 0) != 0;
+  if (!elpo && co_one_sided) cev = CoAppend(p, kern::Seg2{entry, dst, vals.data(), len});
+  hipStream_t stream = nullptr;
+  if (!cev) {
+    stream = elpo ? rplane->StreamForPeer(po_->node_id()) : StreamForPeer(p->node.id);
+    XPS_HIP_CHECK(hipSetDevice(device_));
+    kern::DenseAssign2(entry, dst, vals.data(), len, stream);
+    g_fused_launches.fetch_add(1, std::memory_order_relaxed);
+  }
   g_fused_assign.fetch_add(1, std::memory_order_relaxed);
   g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
   Message meta_msg;
@@ -657,13 +862,16 @@ bool GpuPlane::EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out) {
     std::vector<char> br(meta_msg.data.size(), 0);
     XPS_CHECK(Serialize(meta_msg, br, &payload));
   }
-  hipEvent_t ev = GetEvent();
-  XPS_HIP_CHECK(hipEventRecord(ev, stream));
+  hipEvent_t ev = nullptr;
+  if (!cev) {
+    ev = GetEvent();
+    XPS_HIP_CHECK(hipEventRecord(ev, stream));
+  }
   {
     std::lock_guard<std::mutex> lk(pend_mu_);
     pending_[p->node.id].push_back(Pending{ev, p->node.id, std::move(payload),
                                            std::move(meta_msg), std::move(keepalive), bytes,
-                                           elpo});
+                                           elpo, std::move(cev)});
   }
   pending_count_.fetch_add(1);
   p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
@@ -768,16 +976,22 @@ int64_t GpuPlane::SendLocal(Message& msg, Peer* p, Postoffice* lpo) {
   if (response && device_ >= 0 && !kernel_less_ack) {
     // GPU handler output: deliver once this peer's lane drained
     XPS_STAGE(local_defer);
-    hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(p->node.id)
-                                                          : StreamForPeer(p->node.id);
-    hipEvent_t ev = GetEvent();
-    XPS_HIP_CHECK(hipSetDevice(device_));
-    XPS_HIP_CHECK(hipEventRecord(ev, stream));
+    // the handler's coalesced dual write: no event of its own, the entry
+    // waits for the shared event of its batch
+    std::shared_ptr<CoEvent> cev = TakeTicket(p->node.id);
+    hipEvent_t ev = nullptr;
+    if (!cev) {
+      hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(p->node.id)
+                                                            : StreamForPeer(p->node.id);
+      ev = GetEvent();
+      XPS_HIP_CHECK(hipSetDevice(device_));
+      XPS_HIP_CHECK(hipEventRecord(ev, stream));
+    }
     Message resend = msg;
     {
       std::lock_guard<std::mutex> lk(pend_mu_);
       pending_[p->node.id].push_back(Pending{ev, p->node.id, std::string(), std::move(resend),
-                                             Message(), bytes, lpo});
+                                             Message(), bytes, lpo, std::move(cev)});
     }
     pending_count_.fetch_add(1);
   } else {
@@ -1066,16 +1280,37 @@ void GpuPlane::CompletionLoop() {
       for (int id : ids) {
         while (!stop_.load()) {
           hipEvent_t front_ev = nullptr;
+          std::shared_ptr<CoEvent> cev;
           {
             std::lock_guard<std::mutex> lk(pend_mu_);
             auto& dq = pending_[id];
             if (dq.empty()) break;
             front_ev = dq.front().ev;
+            cev = dq.front().cev;
           }
-          hipError_t e = hipEventQuery(front_ev);
-          if (e == hipErrorNotReady) break;
+          bool retired = false;
+          if (cev) {
+            // entry of a coalesced launch: not ready before its batch is
+            // launched (this thread launches a batch that reached the
+            // front); one successful query then releases every
+            // consecutive entry of the batch
+            front_ev = cev->ev.load(std::memory_order_acquire);
+            if (!front_ev) {
+              if (!CoFrontUnlaunched(GetPeer(id), cev)) break;
+              continue;
+            }
+          }
+          if (!cev || !cev->done.load(std::memory_order_acquire)) {
+            hipError_t e = hipEventQuery(front_ev);
+            if (e == hipErrorNotReady) break;
+            XPS_CHECK(e == hipSuccess) << "hipEventQuery: " << hipGetErrorString(e);
+            if (cev) {
+              cev->done.store(true, std::memory_order_release);
+              retired = true;
+            }
+          }
           XPS_STAGE(defer_release);
-          XPS_CHECK(e == hipSuccess) << "hipEventQuery: " << hipGetErrorString(e);
+          if (retired) CoRetired(GetPeer(id));
           Pending front;
           {
             std::lock_guard<std::mutex> lk(pend_mu_);
@@ -1086,7 +1321,7 @@ void GpuPlane::CompletionLoop() {
           pending_count_.fetch_sub(1);
           if (front.local_po) {  // same-process: direct delivery
             DeliverLocal(front.local_po, front.resend, front.bytes);
-            PutEvent(front.ev);
+            if (front.ev) PutEvent(front.ev);  // a coalesced entry's event is shared
             did = true;
             continue;
           }
@@ -1106,7 +1341,7 @@ void GpuPlane::CompletionLoop() {
                                << " failed too (peer dead?)";
             }
           }
-          PutEvent(front.ev);
+          if (front.ev) PutEvent(front.ev);  // a coalesced entry's event is shared
           did = true;
         }
       }

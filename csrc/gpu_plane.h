@@ -25,6 +25,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "kernels.h"
 #include "shm_ring.h"
 #include "van.h"
 
@@ -40,6 +41,12 @@ extern std::atomic<uint64_t> g_fused_assign;
 // XPS_FUSED_ASSIGN (default 1): 0 restores the two-kernel push-then-pull
 // everywhere (A/B runs within one build)
 bool FusedAssignEnabled();
+// dual-write LAUNCHES (direct or coalesced): equals g_fused_assign when
+// every key has its own launch, smaller when queued keys shared launches
+extern std::atomic<uint64_t> g_fused_launches;
+// XPS_COALESCE (default 1): 0 gives every fused key its own launch and
+// event again (A/B runs within one build)
+bool CoalesceEnabled();
 
 class Postoffice;
 
@@ -66,6 +73,25 @@ class GpuPlane : public DataPlane {
   hipStream_t StreamForPeer(int node_id);      // lane 0: push/compute
   hipStream_t PullStreamForPeer(int node_id);  // pull-response lane
   int lanes() const { return lanes_; }
+  // do this peer's two lanes differ (cross-device)? Hands out no stream,
+  // so unlike the two accessors above it leaves an open batch alone.
+  bool LanesSplit(int node_id);
+
+  // ---- dual-write launch coalescer (one open batch per lane-0 stream) --
+  // Fused push+pull keys that arrive while the GPU is busy ride ONE
+  // batched launch and ONE event. An open batch counts as already
+  // enqueued on its stream: StreamForPeer / PullStreamForPeer (and every
+  // internal lane-0 use) launch it before handing the stream out, so all
+  // other stream work stays ordered behind it.
+  // Handler side: append `seg` to the open batch of `peer_id`'s lane 0.
+  // False = not batched (switch off, misaligned, ...): the open batch was
+  // launched and the caller launches the segment itself. True = the
+  // response the caller sends next ON THIS THREAD to that peer is
+  // deferred on the batch's shared event; call CoalesceEnd right after.
+  bool CoalesceAppend(int peer_id, const kern::Seg2& seg);
+  // closes CoalesceAppend: if no deferred response picked the batch up
+  // (it left on another path), launch the batch so the write still runs
+  void CoalesceEnd(int peer_id);
   // per-peer traffic counters: (node id, tx bytes, rx bytes) — the
   // per-link utilization report of SURVEY §5.8 (each peer pair rides
   // its own xGMI link)
@@ -89,8 +115,33 @@ class GpuPlane : public DataPlane {
   }
 
  private:
+  // completion of one coalesced launch, shared by every Pending of its
+  // batch: ev stays null until the batch is launched, then holds the one
+  // recorded event; it returns to the pool with the last reference
+  struct CoEvent {
+    explicit CoEvent(GpuPlane* pl) : plane(pl) {}
+    ~CoEvent() {
+      if (hipEvent_t e = ev.load(std::memory_order_acquire)) plane->PutEvent(e);
+    }
+    GpuPlane* plane;
+    std::atomic<hipEvent_t> ev{nullptr};
+    std::atomic<bool> done{false};  // set by the completion thread
+    size_t bytes = 0;               // payload of the launch
+  };
+  struct Coalescer {
+    std::mutex mu;
+    kern::Seg2 segs[kern::kMaxBatch];
+    int n = 0;
+    std::atomic<int> n_open{0};  // == n, readable without mu
+    size_t bytes = 0;
+    std::shared_ptr<CoEvent> open;                 // event-to-be of the open batch
+    std::deque<std::shared_ptr<CoEvent>> inflight;  // launched, not seen complete
+    int64_t last_append_us = 0;                    // XPS_COALESCE_HOLD quiescence
+  };
+
   struct Peer {
     Node node;
+    Coalescer co;
     // set when this peer's Postoffice lives in OUR process (joint
     // mode): sends bypass serialize/ring/poll entirely (direct call)
     std::atomic<Postoffice*> local_po{nullptr};
@@ -112,7 +163,7 @@ class GpuPlane : public DataPlane {
   };
 
   struct Pending {
-    hipEvent_t ev;
+    hipEvent_t ev;  // null when cev is set
     int peer_id;
     std::string payload;
     // TCP-resendable form of this message: if the ring push fails after
@@ -124,6 +175,7 @@ class GpuPlane : public DataPlane {
     Message keepalive;  // holds pool temporaries until the event fires
     int64_t bytes;
     Postoffice* local_po = nullptr;  // same-process: deliver, don't ring-push
+    std::shared_ptr<CoEvent> cev;    // coalesced launch this entry waits for
   };
 
   Peer* GetPeer(int id);
@@ -151,7 +203,21 @@ class GpuPlane : public DataPlane {
   bool Serialize(const Message& msg, const std::vector<char>& by_ref, std::string* out);
   void RingPollLoop();
   void CompletionLoop();
+  // lane 0 launches the open batch first (see the coalescer above)
   hipStream_t StreamLane(int node_id, int lane);
+  hipStream_t RawLane(Peer* p, int lane);  // no flush: the coalescing path only
+  // coalescer internals; *Locked run under p->co.mu
+  std::shared_ptr<CoEvent> CoAppend(Peer* p, const kern::Seg2& seg);
+  void CoLaunchLocked(Peer* p);
+  void CoPruneLocked(Peer* p);
+  bool CoBusyLocked(Peer* p);  // prunes, then: is the GPU this stream's bottleneck?
+  void CoFlush(Peer* p);
+  // completion thread: an entry of an unlaunched batch reached the front
+  // of its queue; true once the batch is launched
+  bool CoFrontUnlaunched(Peer* p, const std::shared_ptr<CoEvent>& cev);
+  void CoRetired(Peer* p);  // completion thread: a batch of p completed
+  // this thread's pending CoalesceAppend ticket for peer_id, if any
+  std::shared_ptr<CoEvent> TakeTicket(int peer_id);
   // One-sided fused push+pull (request carries kOptEntryPush with the
   // cached entry offset in meta.entry_addr and our own pull destination
   // in meta.addr): ONE dual-write kernel of ours stores vals to the
@@ -166,6 +232,8 @@ class GpuPlane : public DataPlane {
   Postoffice* po_;
   int device_;
   int lanes_ = 2;  // XPS_STREAMS_PER_PEER
+  bool co_hold_ = false;             // XPS_COALESCE_HOLD (tests only)
+  size_t co_byte_cap_ = 1ull << 30;  // XPS_COALESCE_CAP_MB
   uint64_t my_host_hash_;
   ShmRing in_ring_;
   bool started_ = false;

@@ -11,6 +11,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "coalesce_admit.h"
+
 namespace xps {
 namespace kern {
 
@@ -71,6 +73,16 @@ struct CopyDesc {
 };
 void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s);
 void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s);
+
+// Batched dual write: dst0[i] = dst1[i] = src[i] for every segment, in
+// one launch per kMaxBatch segments (the coalesced form of DenseAssign2:
+// keys queued behind a busy GPU share one launch). Every segment needs
+// its three pointers 16 B-aligned, nbytes % 16 == 0 and pairwise-disjoint
+// ranges; segments of one call must not conflict with each other
+// (CoalesceAdmit). tile_cap > 0 caps the grid (tests use it to force
+// several tile iterations per block on small inputs).
+static_assert(kMaxBatch2 == kMaxBatch, "Seg2 batches use the batched kernels' segment limit");
+void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap = 0);
 
 }  // namespace kern
 }  // namespace xps

@@ -320,6 +320,68 @@ __global__ void batched_balanced_kernel(BalancedDescArray da, size_t chunks_per_
   }
 }
 
+struct Seg2Array {
+  Seg2 d[kMaxBatch];
+  unsigned long long prefix[kMaxBatch + 1];  // chunk offsets, prefix[n] = total
+  int n;
+};
+
+// Dual-write counterpart of the balanced kernel: up to kMaxBatch fused
+// push+pull segments concatenated in the 16 B-chunk prefix space, one
+// 16 B load and two 16 B stores per lane per iteration (plain stores, no
+// unrolling — the assign2_kernel variants table settled that). No
+// segment is empty, so prefix is strictly increasing and the forward
+// walk below always ends at seg + 1 <= n.
+// Each block owns one contiguous tile of chunks_per_block chunks. The
+// alternative, a grid-stride sweep over the concatenated space (the
+// access pattern of assign2_kernel), was run against it on the
+// 128 x 64 MiB headline, 5 alternating runs: tiles 3847-3917 GB/s, grid
+// stride 3750-3798 (profiles/dense64_coalesced_rocprof.md) — tiles kept.
+__global__ void batched_assign2_kernel(Seg2Array da, size_t chunks_per_block) {
+  size_t total = da.prefix[da.n];
+  size_t first = blockIdx.x * chunks_per_block;
+  size_t end = first + chunks_per_block;
+  if (end > total) end = total;
+  if (first >= end) return;
+  const size_t step = blockDim.x;
+  size_t begin = first + threadIdx.x;
+  // segment of the block's first chunk (block-uniform binary search),
+  // then every lane walks forward from there
+  int seg = 0;
+  {
+    int lo = 0, hi = da.n - 1;
+    while (lo < hi) {
+      int mid = (lo + hi + 1) >> 1;
+      if (da.prefix[mid] <= first) {
+        lo = mid;
+      } else {
+        hi = mid - 1;
+      }
+    }
+    seg = lo;
+  }
+  size_t seg_lo = da.prefix[seg], seg_hi = da.prefix[seg + 1];
+  uint4* d0 = static_cast<uint4*>(da.d[seg].dst0);
+  uint4* d1 = static_cast<uint4*>(da.d[seg].dst1);
+  const uint4* sp = static_cast<const uint4*>(da.d[seg].src);
+  for (size_t g = begin; g < end; g += step) {
+    if (g >= seg_hi) {
+      do {
+        ++seg;
+        seg_hi = da.prefix[seg + 1];
+      } while (g >= seg_hi);
+      seg_lo = da.prefix[seg];
+      d0 = static_cast<uint4*>(da.d[seg].dst0);
+      d1 = static_cast<uint4*>(da.d[seg].dst1);
+      sp = static_cast<const uint4*>(da.d[seg].src);
+    }
+    size_t local = g - seg_lo;
+    uint4 v = sp[local];
+    d0[local] = v;
+    d1[local] = v;
+  }
+}
+
 // every block strides over every segment's 16B chunks (grid sized for
 // the concatenated total, so all segments together fill the 8 XCDs)
 // (segment loop per block; fine for <= kMaxBatch segments)
@@ -421,6 +483,30 @@ void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s) {
     da.n = std::min(n - off, kMaxBatch);
     for (int i = 0; i < da.n; ++i) da.d[i] = descs_host[off + i];
     hipLaunchKernelGGL(batched_assign_kernel, dim3(GridFor(total / 16)), dim3(kBlock), 0, s, da);
+  }
+}
+
+void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap) {
+  int max_blocks = tile_cap > 0 ? std::min(tile_cap, 8192) : 8192;
+  int off = 0;
+  while (off < n) {
+    Seg2Array da{};
+    unsigned long long acc = 0;
+    while (off < n && da.n < kMaxBatch) {
+      const Seg2& sg = segs_host[off++];
+      if (sg.nbytes < 16) continue;  // keeps prefix strictly increasing
+      da.d[da.n] = sg;
+      da.prefix[da.n] = acc;
+      acc += sg.nbytes / 16;
+      ++da.n;
+    }
+    da.prefix[da.n] = acc;
+    if (acc == 0) continue;
+    // tile size: whole multiples of the block so lanes sweep full strides
+    size_t cpb = (acc + max_blocks - 1) / max_blocks;
+    cpb = ((cpb + kBlock - 1) / kBlock) * kBlock;
+    int grid = static_cast<int>((acc + cpb - 1) / cpb);
+    hipLaunchKernelGGL(batched_assign2_kernel, dim3(grid), dim3(kBlock), 0, s, da, cpb);
   }
 }
 

@@ -574,6 +574,27 @@ PYBIND11_MODULE(_core, m) {
   m.def("zero_copy_recv_count", []() { return g_zero_copy_recv.load(); });
   // fused dual-write launches (server fast path + worker one-sided path)
   m.def("fused_assign_count", []() { return g_fused_assign.load(); });
+  m.def("fused_assign_launches", []() { return g_fused_launches.load(); });
+  // the coalescer's admit-or-flush decision (pure host code): segments
+  // are (dst0, dst1, src, nbytes) address tuples, nothing is dereferenced.
+  // Returns "admit", "flush" or "reject".
+  m.def("coalesce_admit",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, size_t>>& open,
+           const std::tuple<uintptr_t, uintptr_t, uintptr_t, size_t>& seg) {
+          auto conv = [](const std::tuple<uintptr_t, uintptr_t, uintptr_t, size_t>& t) {
+            return kern::Seg2{reinterpret_cast<void*>(std::get<0>(t)),
+                              reinterpret_cast<void*>(std::get<1>(t)),
+                              reinterpret_cast<const void*>(std::get<2>(t)), std::get<3>(t)};
+          };
+          std::vector<kern::Seg2> segs;
+          for (auto& t : open) segs.push_back(conv(t));
+          switch (kern::CoalesceAdmit(segs.data(), static_cast<int>(segs.size()), conv(seg))) {
+            case kern::Admit::kAdmit: return "admit";
+            case kern::Admit::kFlushFirst: return "flush";
+            default: return "reject";
+          }
+        },
+        py::arg("open"), py::arg("seg"));
 
   // per-peer plane traffic: {node_id: (tx_bytes, rx_bytes)} — each peer
   // pair rides its own xGMI link, so this is the per-link utilization
@@ -830,6 +851,26 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("dst0"), py::arg("dst1"), py::arg("src"), py::arg("nbytes"),
         py::arg("grid_cap") = 0);
+  m.def("k_batched_assign2",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, size_t>>& segs,
+           int tile_cap) {
+          std::vector<kern::Seg2> v;
+          for (auto& t : segs) {
+            v.push_back(kern::Seg2{reinterpret_cast<void*>(std::get<0>(t)),
+                                   reinterpret_cast<void*>(std::get<1>(t)),
+                                   reinterpret_cast<const void*>(std::get<2>(t)),
+                                   std::get<3>(t)});
+            if (kern::CoalesceAdmit(nullptr, 0, v.back()) != kern::Admit::kAdmit) {
+              throw std::invalid_argument("k_batched_assign2: segment " +
+                                          std::to_string(v.size() - 1) +
+                                          " is misaligned, not a 16 B multiple or "
+                                          "self-overlapping");
+            }
+          }
+          kern::BatchedAssign2(v.data(), static_cast<int>(v.size()), nullptr, tile_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("segs"), py::arg("tile_cap") = 0);
   m.def("k_dense_sum_f32", [](uintptr_t dst, uintptr_t src, size_t n) {
     kern::DenseSumF32(reinterpret_cast<float*>(dst), reinterpret_cast<float*>(src), n, nullptr);
     gpu::DeviceSync(-1);

@@ -89,8 +89,7 @@ bool GpuDenseHandler::NeedChain(int sender) {
   // lane split for this peer (cross-device): push kernels on lane 0 and
   // pull copies on the pull lane touch the same entries — chain them
   auto* plane = ThePlane(po_);
-  return plane && plane->lanes() > 1 &&
-         plane->PullStreamForPeer(sender) != plane->StreamForPeer(sender);
+  return plane && plane->LanesSplit(sender);
 }
 
 GpuDenseHandler::~GpuDenseHandler() = default;
@@ -174,12 +173,22 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
   if (e->buf.size() != len) return false;
   const char* src = reinterpret_cast<const char*>(kvs.vals.data());
   if (!kern::Disjoint3(e->buf.data(), dst, src, len)) return false;
-  hipStream_t stream = Stream(req.sender);
-  OrderAfter(e, stream);
-  kern::DenseAssign2(e->buf.data(), dst, src, len, stream);
+  // Queued behind a busy GPU the key joins the open batch of the sender's
+  // lane and shares its launch and event (GpuPlane's coalescer). Senders
+  // that need the last_ev chain keep their own launch: the chain wants an
+  // event per key.
+  bool chain = NeedChain(req.sender);
+  bool coalesced = !chain && !e->last_ev &&
+                   plane->CoalesceAppend(req.sender, kern::Seg2{e->buf.data(), dst, src, len});
+  if (!coalesced) {
+    hipStream_t stream = Stream(req.sender);
+    OrderAfter(e, stream);
+    kern::DenseAssign2(e->buf.data(), dst, src, len, stream);
+    g_fused_launches.fetch_add(1, std::memory_order_relaxed);
+    if (chain) e->last_ev = MakeEventRef(po_, stream);
+  }
   g_fused_assign.fetch_add(1, std::memory_order_relaxed);
   g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-  if (NeedChain(req.sender)) e->last_ev = MakeEventRef(po_, stream);
   // meta-only in-place response; the work ran on the PUSH lane, so no
   // kOptPullLane — the plane defers delivery on that lane's event. The
   // entry advert rides along so the worker can go one-sided next time.
@@ -193,6 +202,7 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
     r.option |= kOptEntryAddr;
   }
   server->Response(r);
+  if (coalesced) plane->CoalesceEnd(req.sender);
   return true;
 }
 
