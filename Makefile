@@ -67,6 +67,15 @@ cppbench: $(CORE_OBJS) build/bench_kv.o
 	$(HIPCC) $(CPPBENCH_LD) build/bench_kv.o $(CORE_OBJS) \
 	    -o build/bench_kv -lpthread
 
+# one-process sweep of the dual-write kernel shapes (no cluster, no
+# Python; links kernels.hip only): build/bench_dualwrite
+build/bench_dualwrite.o: examples/cpp/bench_dualwrite.hip csrc/*.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_dualwrite.hip -o build/bench_dualwrite.o
+dualwritebench: build/csrc/kernels.hip.o build/bench_dualwrite.o
+	$(HIPCC) $(CPPBENCH_LD) build/bench_dualwrite.o build/csrc/kernels.hip.o \
+	    -o build/bench_dualwrite
+
 # self-contained lint gate (reference parity: tests/lint.py + make lint)
 lint:
 	python3 scripts/lint.py
@@ -76,4 +85,4 @@ lint:
 check: all lint
 	python3 -m pytest tests -q -m "not gpu"
 
-.PHONY: all clean cppbench lint check
+.PHONY: all clean cppbench dualwritebench lint check

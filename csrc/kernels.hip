@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "tile_runs.h"
 
 namespace xps {
 namespace kern {
@@ -28,8 +29,10 @@ inline int GridFor(size_t work_items, int cap = 8192) {
 }
 
 // NOTE: nontemporal loads/stores were measured 3 % SLOWER end-to-end
-// here — the 256 MiB Infinity Cache serves a following pull's re-read of
-// the just-written store, and nt stores bypass it. Keep plain float4.
+// here, with the push and the pull as two kernels (the pull re-read the
+// just-written store). Keep plain float4. For the dual-write kernels
+// below, which have no such re-read, the hints were measured again and
+// lost again (see batched_assign2_kernel).
 __global__ void assign_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n4) {
   size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
@@ -55,6 +58,13 @@ __global__ void assign_tail_kernel(char* __restrict__ dst, const char* __restric
 // longer re-read by this round's pull) 3327-3397, inside that spread, so
 // not adopted; 2 loads in flight per lane 3026-3069 and 2 loads + nt
 // 3226-3244, both slower; 4 loads in flight 3294-3401, no gain.
+// The sweep behind the batched kernel's 8 KiB tiles
+// (profiles/dense64_dualwrite_rocprof.md) left this kernel as it is: its
+// loop already has uniform pointers and issues the next load ahead of the
+// wait on the stores, and one 64 MiB key is 8192 blocks of two strides
+// each, the geometry the sweep chose, swept as a grid stride where the
+// batched kernel sweeps a tile. It runs from two processes at once in the
+// shared-GPU config, which was not to be disturbed.
 __global__ void assign2_kernel(uint4* __restrict__ dst0, uint4* __restrict__ dst1,
                                const uint4* __restrict__ src, size_t n4, size_t tail_begin,
                                size_t nbytes) {
@@ -328,57 +338,43 @@ struct Seg2Array {
 
 // Dual-write counterpart of the balanced kernel: up to kMaxBatch fused
 // push+pull segments concatenated in the 16 B-chunk prefix space, one
-// 16 B load and two 16 B stores per lane per iteration (plain stores, no
-// unrolling — the assign2_kernel variants table settled that). No
-// segment is empty, so prefix is strictly increasing and the forward
-// walk below always ends at seg + 1 <= n.
-// Each block owns one contiguous tile of chunks_per_block chunks. The
-// alternative, a grid-stride sweep over the concatenated space (the
-// access pattern of assign2_kernel), was run against it on the
-// 128 x 64 MiB headline, 5 alternating runs: tiles 3847-3917 GB/s, grid
-// stride 3750-3798 (profiles/dense64_coalesced_rocprof.md) — tiles kept.
-__global__ void batched_assign2_kernel(Seg2Array da, size_t chunks_per_block) {
-  size_t total = da.prefix[da.n];
-  size_t first = blockIdx.x * chunks_per_block;
-  size_t end = first + chunks_per_block;
-  if (end > total) end = total;
-  if (first >= end) return;
-  const size_t step = blockDim.x;
-  size_t begin = first + threadIdx.x;
-  // segment of the block's first chunk (block-uniform binary search),
-  // then every lane walks forward from there
-  int seg = 0;
-  {
-    int lo = 0, hi = da.n - 1;
-    while (lo < hi) {
-      int mid = (lo + hi + 1) >> 1;
-      if (da.prefix[mid] <= first) {
-        lo = mid;
-      } else {
-        hi = mid - 1;
-      }
+// 16 B load and two 16 B stores per lane per iteration. No segment is
+// empty, so prefix is strictly increasing.
+// Each block owns one contiguous tile of chunks_per_block chunks and
+// takes it apart into runs, one per segment the tile touches
+// (tile_runs.h). The run list comes from block-uniform values only, so
+// the segment table is read with scalar loads and the inner loop has
+// uniform base pointers: the next load is issued while the previous
+// iteration's stores are still in flight. (The earlier form let every
+// lane walk the segment list; its loop waited for the stores to drain
+// ahead of each load.)
+// What was measured (profiles/dense64_dualwrite_rocprof.md; one process,
+// 16 x 64 MiB per launch, variants interleaved, µs per 64 MiB key on the
+// slower / faster of two buffer sets):
+//   per-lane walk, 128 KiB tiles (the shape before)   39.9 / 34.5
+//   runs, 128 KiB tiles                               37.8 / 34.1
+//   runs, 8 KiB tiles (shipped)                       32.9 / 31.6
+// Tile size is the axis that pays: 4-16 KiB are level, 32 KiB is 1 µs
+// behind, 64 KiB and up fall back to the old figure. 2, 4 or 8 loads in
+// flight per lane, blocks of 512 or 1024, a fixed grid of 256*k blocks
+// looping over tiles, a non-power-of-two tile, a rotated start inside
+// the tile and nontemporal hints on any of the three streams were each
+// inside the noise or slower, so none of them is here.
+constexpr size_t kTileChunks2 = 512;  // 8 KiB per block, two strides of the block
+
+__global__ void __launch_bounds__(kBlock)
+    batched_assign2_kernel(Seg2Array da, size_t chunks_per_block) {
+  TileRunIter it = TileRunsBegin(da.prefix, da.n, chunks_per_block, blockIdx.x);
+  TileRun run;
+  while (TileRunsNext(da.prefix, &it, &run)) {
+    uint4* __restrict__ d0 = static_cast<uint4*>(da.d[run.seg].dst0);
+    uint4* __restrict__ d1 = static_cast<uint4*>(da.d[run.seg].dst1);
+    const uint4* __restrict__ sp = static_cast<const uint4*>(da.d[run.seg].src);
+    for (size_t i = run.lo + threadIdx.x; i < run.hi; i += kBlock) {
+      uint4 v = sp[i];
+      d0[i] = v;
+      d1[i] = v;
     }
-    seg = lo;
-  }
-  size_t seg_lo = da.prefix[seg], seg_hi = da.prefix[seg + 1];
-  uint4* d0 = static_cast<uint4*>(da.d[seg].dst0);
-  uint4* d1 = static_cast<uint4*>(da.d[seg].dst1);
-  const uint4* sp = static_cast<const uint4*>(da.d[seg].src);
-  for (size_t g = begin; g < end; g += step) {
-    if (g >= seg_hi) {
-      do {
-        ++seg;
-        seg_hi = da.prefix[seg + 1];
-      } while (g >= seg_hi);
-      seg_lo = da.prefix[seg];
-      d0 = static_cast<uint4*>(da.d[seg].dst0);
-      d1 = static_cast<uint4*>(da.d[seg].dst1);
-      sp = static_cast<const uint4*>(da.d[seg].src);
-    }
-    size_t local = g - seg_lo;
-    uint4 v = sp[local];
-    d0[local] = v;
-    d1[local] = v;
   }
 }
 
@@ -502,9 +498,13 @@ void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap) {
     }
     da.prefix[da.n] = acc;
     if (acc == 0) continue;
-    // tile size: whole multiples of the block so lanes sweep full strides
+    // tile size: whole multiples of the block so lanes sweep full
+    // strides, enough for ~8192 blocks on a small launch, and no more
+    // than kTileChunks2 however large the launch (past 64 MiB the grid
+    // grows instead of the tile). A tile_cap is obeyed as given.
     size_t cpb = (acc + max_blocks - 1) / max_blocks;
     cpb = ((cpb + kBlock - 1) / kBlock) * kBlock;
+    if (tile_cap <= 0 && cpb > kTileChunks2) cpb = kTileChunks2;
     int grid = static_cast<int>((acc + cpb - 1) / cpb);
     hipLaunchKernelGGL(batched_assign2_kernel, dim3(grid), dim3(kBlock), 0, s, da, cpb);
   }

@@ -18,6 +18,7 @@
 #include "server_handlers.h"
 #include "shm_ring.h"
 #include "simple_app.h"
+#include "tile_runs.h"
 #include "van.h"
 #include "wire.h"
 
@@ -595,6 +596,31 @@ PYBIND11_MODULE(_core, m) {
           }
         },
         py::arg("open"), py::arg("seg"));
+  // the batched dual-write kernel's run enumeration (tile_runs.h, the
+  // same code the kernel runs): the (segment, lo, hi) runs of block
+  // block_index when segments of chunk_counts 16 B chunks are
+  // concatenated and every block owns chunks_per_block of them. lo and hi
+  // count from the segment's start, hi is exclusive.
+  m.def("tile_runs",
+        [](const std::vector<unsigned long long>& chunk_counts,
+           unsigned long long chunks_per_block, unsigned long long block_index) {
+          if (chunks_per_block == 0) throw std::invalid_argument("tile_runs: empty tile");
+          std::vector<unsigned long long> prefix(chunk_counts.size() + 1, 0);
+          for (size_t i = 0; i < chunk_counts.size(); ++i) {
+            if (chunk_counts[i] == 0) throw std::invalid_argument("tile_runs: empty segment");
+            prefix[i + 1] = prefix[i] + chunk_counts[i];
+          }
+          int n = static_cast<int>(chunk_counts.size());
+          std::vector<std::tuple<int, unsigned long long, unsigned long long>> out;
+          kern::TileRunIter it = kern::TileRunsBegin(prefix.data(), n, chunks_per_block,
+                                                     block_index);
+          kern::TileRun run;
+          while (kern::TileRunsNext(prefix.data(), &it, &run)) {
+            out.emplace_back(run.seg, run.lo, run.hi);
+          }
+          return out;
+        },
+        py::arg("chunk_counts"), py::arg("chunks_per_block"), py::arg("block_index"));
 
   // per-peer plane traffic: {node_id: (tx_bytes, rx_bytes)} — each peer
   // pair rides its own xGMI link, so this is the per-link utilization
