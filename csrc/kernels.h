@@ -16,8 +16,13 @@
 namespace xps {
 namespace kern {
 
-// dst[i] = src[i] (bytes; 16B-vectorized grid-stride copy kernel)
-void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s);
+// dst[i] = src[i] (bytes; 16B-vectorized grid-stride copy kernel).
+// DenseAssign, DenseSumF32 and DenseSumBf16 take the 16 B kernel when dst
+// and src are both 16 B-aligned (pool buffers are) and an element-wise
+// grid-stride kernel for the whole range when either is not. grid_cap > 0
+// caps the grid (tests use it to force many grid-stride iterations on a
+// small buffer); 0 leaves the launch as it is.
+void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s, int grid_cap = 0);
 // dst0[i] = dst1[i] = src[i] (bytes; one 16 B load, two 16 B stores per
 // lane — the fused push+pull of one key). The three ranges must be
 // pairwise disjoint. grid_cap > 0 caps the grid (tests use it to force
@@ -34,12 +39,12 @@ inline bool Disjoint3(const void* a, const void* b, const void* c, size_t len) {
   return apart(a, b) && apart(a, c) && apart(b, c);
 }
 // dst[i] += src[i] (fp32)
-void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s);
+void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s, int grid_cap = 0);
 // dst[i] += src[i] (bf16 payloads, fp32 accumulate in-register,
 // round-to-nearest-even back to bf16 — halves bytes moved on the
 // bandwidth-bound dense path)
-void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s);
-void BatchedSumBf16(const struct CopyDesc* descs_host, int n, hipStream_t s);
+void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s, int grid_cap = 0);
+void BatchedSumBf16(const struct CopyDesc* descs_host, int n, hipStream_t s, int tile_cap = 0);
 // dst[i] += sum_j srcs[j][i], up to 8 sources in one pass (one read of
 // dst, one write — HBM-optimal multi-worker reduction)
 // Sparse ops: local row index = (rows[r] >> key_shift) - row_base, so a
@@ -48,19 +53,20 @@ void BatchedSumBf16(const struct CopyDesc* descs_host, int n, hipStream_t s);
 // table_rows bounds every decoded row index: out-of-range rows (corrupt
 // or misrouted keys) are skipped by scatters and read as zeros by
 // gathers, never touching memory outside the table. The ~0 default
-// disables the check (trusted keys).
+// disables the check (trusted keys). grid_cap > 0 caps the grid (tests).
 // out[r][:] = table[row(r)][:] for r in [0, nrows)
 void SparseGatherF32(const float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                      float* out, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
-                     uint64_t table_rows = ~0ull);
+                     uint64_t table_rows = ~0ull, int grid_cap = 0);
 // table[row(r)][:] += src[r][:]; atomic=true tolerates duplicate rows
 void SparseScatterAddF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                          const float* src, bool atomic, hipStream_t s, int key_shift = 0,
-                         uint64_t row_base = 0, uint64_t table_rows = ~0ull);
+                         uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
 // table[row(r)][:] = src[r][:]
 void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                             const float* src, hipStream_t s, int key_shift = 0,
-                            uint64_t row_base = 0, uint64_t table_rows = ~0ull);
+                            uint64_t row_base = 0, uint64_t table_rows = ~0ull,
+                            int grid_cap = 0);
 
 // Batched segmented copy/accumulate: one launch serving up to
 // kMaxBatch (dst, src, nbytes) segments — the device-side slicing/merge
@@ -71,8 +77,11 @@ struct CopyDesc {
   const void* src;
   size_t nbytes;  // must be 16B-multiples for the batched kernels
 };
-void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s);
-void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s);
+// Segments may be empty. tile_cap > 0 caps the number of blocks (tests):
+// on the balanced path the tile grows and a block sweeps several strides
+// of it, on the XPS_BALANCED_BATCH=0 path the grid-stride grid shrinks.
+void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap = 0);
+void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap = 0);
 
 // Batched dual write: dst0[i] = dst1[i] = src[i] for every segment, in
 // one launch per kMaxBatch segments (the coalesced form of DenseAssign2:

@@ -28,6 +28,9 @@ inline int GridFor(size_t work_items, int cap = 8192) {
   return static_cast<int>(g);
 }
 
+// test-only grid caps (grid_cap / tile_cap arguments): 0 leaves the grid as is
+inline int CapGrid(int grid, int cap) { return cap > 0 && grid > cap ? cap : grid; }
+
 // NOTE: nontemporal loads/stores were measured 3 % SLOWER end-to-end
 // here, with the push and the pull as two kernels (the pull re-read the
 // just-written store). Keep plain float4. For the dual-write kernels
@@ -39,10 +42,15 @@ __global__ void assign_kernel(uint4* __restrict__ dst, const uint4* __restrict__
   for (; i < n4; i += stride) dst[i] = src[i];
 }
 
+// The element kernels (bytes here, floats and bf16 below) serve two
+// launches: one block for the sub-16 B tail [n4 * 16, nbytes) of an
+// aligned range, and a grid-stride sweep of a whole range [0, n) whose
+// pointers are not 16 B-aligned.
 __global__ void assign_tail_kernel(char* __restrict__ dst, const char* __restrict__ src,
                                    size_t begin, size_t end) {
   size_t i = begin + blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i < end) dst[i] = src[i];
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < end; i += stride) dst[i] = src[i];
 }
 
 // Fused push+pull of one key: one 16 B load per lane per iteration, two
@@ -103,7 +111,8 @@ __global__ void sum_kernel_f32(float4* __restrict__ dst, const float4* __restric
 __global__ void sum_tail_f32(float* __restrict__ dst, const float* __restrict__ src, size_t begin,
                              size_t end) {
   size_t i = begin + blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i < end) dst[i] += src[i];
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < end; i += stride) dst[i] += src[i];
 }
 
 // bf16 += bf16 with fp32 accumulate in-register, 16 B per lane (8 bf16
@@ -154,7 +163,10 @@ __global__ void sum_kernel_bf16(uint4* __restrict__ dst, const uint4* __restrict
 __global__ void sum_tail_bf16(uint16_t* __restrict__ dst, const uint16_t* __restrict__ src,
                               size_t begin, size_t end) {
   size_t i = begin + blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i < end) dst[i] = f32_to_bf16(bf16_to_f32(dst[i]) + bf16_to_f32(src[i]));
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < end; i += stride) {
+    dst[i] = f32_to_bf16(bf16_to_f32(dst[i]) + bf16_to_f32(src[i]));
+  }
 }
 
 // flat indexing: thread i handles element i of the CONCATENATED rows
@@ -443,7 +455,8 @@ bool BalancedBatchEnabled() {
 }
 
 template <int kOp>
-void LaunchBalanced(const CopyDesc* descs_host, int n, hipStream_t s) {
+void LaunchBalanced(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap) {
+  size_t max_blocks = tile_cap > 0 ? std::min(tile_cap, 8192) : 8192;
   for (int off = 0; off < n; off += kMaxBatch) {
     BalancedDescArray da{};
     da.n = std::min(n - off, kMaxBatch);
@@ -456,8 +469,9 @@ void LaunchBalanced(const CopyDesc* descs_host, int n, hipStream_t s) {
     da.prefix[da.n] = acc;
     if (acc == 0) continue;
     // tile size: fill ~8192 blocks (8 XCDs want >> 256 workgroups),
-    // whole multiples of the block so lanes sweep full strides
-    size_t cpb = (acc + 8191) / 8192;
+    // whole multiples of the block so lanes sweep full strides (under a
+    // tile_cap the tile grows and a block sweeps several strides of it)
+    size_t cpb = (acc + max_blocks - 1) / max_blocks;
     cpb = ((cpb + kBlock - 1) / kBlock) * kBlock;
     int grid = static_cast<int>((acc + cpb - 1) / cpb);
     hipLaunchKernelGGL((batched_balanced_kernel<kOp>), dim3(grid), dim3(kBlock), 0, s, da,
@@ -465,21 +479,37 @@ void LaunchBalanced(const CopyDesc* descs_host, int n, hipStream_t s) {
   }
 }
 
-}  // namespace
-
-void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s) {
-  if (BalancedBatchEnabled()) {
-    LaunchBalanced<0>(descs_host, n, s);
-    return;
-  }
+// XPS_BALANCED_BATCH=0: every block strides over every segment, the grid
+// sized for the concatenated total
+template <typename Kernel>
+void LaunchLegacy(Kernel kernel, const CopyDesc* descs_host, int n, hipStream_t s,
+                  int tile_cap) {
   size_t total = 0;
   for (int i = 0; i < n; ++i) total += descs_host[i].nbytes;
+  if (total < 16) return;  // nothing but empty segments
+  int grid = CapGrid(GridFor(total / 16), tile_cap);
   DescArray da{};
   for (int off = 0; off < n; off += kMaxBatch) {
     da.n = std::min(n - off, kMaxBatch);
     for (int i = 0; i < da.n; ++i) da.d[i] = descs_host[off + i];
-    hipLaunchKernelGGL(batched_assign_kernel, dim3(GridFor(total / 16)), dim3(kBlock), 0, s, da);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, da);
   }
+}
+
+// the 16 B kernels need both pointers 16 B-aligned (pool buffers are);
+// anything else takes the element kernel for the whole range
+inline bool Aligned16(const void* a, const void* b) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+}
+
+}  // namespace
+
+void BatchedAssign(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap) {
+  if (BalancedBatchEnabled()) {
+    LaunchBalanced<0>(descs_host, n, s, tile_cap);
+    return;
+  }
+  LaunchLegacy(batched_assign_kernel, descs_host, n, s, tile_cap);
 }
 
 void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap) {
@@ -510,25 +540,25 @@ void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap) {
   }
 }
 
-void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s) {
+void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap) {
   if (BalancedBatchEnabled()) {
-    LaunchBalanced<1>(descs_host, n, s);
+    LaunchBalanced<1>(descs_host, n, s, tile_cap);
     return;
   }
-  size_t total = 0;
-  for (int i = 0; i < n; ++i) total += descs_host[i].nbytes;
-  DescArray da{};
-  for (int off = 0; off < n; off += kMaxBatch) {
-    da.n = std::min(n - off, kMaxBatch);
-    for (int i = 0; i < da.n; ++i) da.d[i] = descs_host[off + i];
-    hipLaunchKernelGGL(batched_sum_kernel_f32, dim3(GridFor(total / 16)), dim3(kBlock), 0, s, da);
-  }
+  LaunchLegacy(batched_sum_kernel_f32, descs_host, n, s, tile_cap);
 }
 
-void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s) {
+void DenseAssign(void* dst, const void* src, size_t nbytes, hipStream_t s, int grid_cap) {
+  if (!Aligned16(dst, src)) {
+    if (nbytes == 0) return;
+    hipLaunchKernelGGL(assign_tail_kernel, dim3(CapGrid(GridFor(nbytes), grid_cap)),
+                       dim3(kBlock), 0, s, static_cast<char*>(dst),
+                       static_cast<const char*>(src), size_t{0}, nbytes);
+    return;
+  }
   size_t n4 = nbytes / 16;
   if (n4) {
-    hipLaunchKernelGGL(assign_kernel, dim3(GridFor(n4)), dim3(kBlock), 0, s,
+    hipLaunchKernelGGL(assign_kernel, dim3(CapGrid(GridFor(n4), grid_cap)), dim3(kBlock), 0, s,
                        static_cast<uint4*>(dst), static_cast<const uint4*>(src), n4);
   }
   if (nbytes % 16) {
@@ -552,10 +582,16 @@ void DenseAssign2(void* dst0, void* dst1, const void* src, size_t nbytes, hipStr
                      nbytes);
 }
 
-void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s) {
+void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s, int grid_cap) {
+  if (!Aligned16(dst, src)) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(sum_tail_f32, dim3(CapGrid(GridFor(n), grid_cap)), dim3(kBlock), 0, s, dst,
+                       src, size_t{0}, n);
+    return;
+  }
   size_t n4 = n / 4;
   if (n4) {
-    hipLaunchKernelGGL(sum_kernel_f32, dim3(GridFor(n4)), dim3(kBlock), 0, s,
+    hipLaunchKernelGGL(sum_kernel_f32, dim3(CapGrid(GridFor(n4), grid_cap)), dim3(kBlock), 0, s,
                        reinterpret_cast<float4*>(dst), reinterpret_cast<const float4*>(src), n4);
   }
   if (n % 4) {
@@ -563,10 +599,16 @@ void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s) {
   }
 }
 
-void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s) {
+void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s, int grid_cap) {
+  if (!Aligned16(dst, src)) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(sum_tail_bf16, dim3(CapGrid(GridFor(n), grid_cap)), dim3(kBlock), 0, s,
+                       dst, src, size_t{0}, n);
+    return;
+  }
   size_t n8 = n / 8;
   if (n8) {
-    hipLaunchKernelGGL(sum_kernel_bf16, dim3(GridFor(n8)), dim3(kBlock), 0, s,
+    hipLaunchKernelGGL(sum_kernel_bf16, dim3(CapGrid(GridFor(n8), grid_cap)), dim3(kBlock), 0, s,
                        reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), n8);
   }
   if (n % 8) {
@@ -574,59 +616,58 @@ void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s) {
   }
 }
 
-void BatchedSumBf16(const CopyDesc* descs_host, int n, hipStream_t s) {
+void BatchedSumBf16(const CopyDesc* descs_host, int n, hipStream_t s, int tile_cap) {
   if (BalancedBatchEnabled()) {
-    LaunchBalanced<2>(descs_host, n, s);
+    LaunchBalanced<2>(descs_host, n, s, tile_cap);
     return;
   }
-  size_t total = 0;
-  for (int i = 0; i < n; ++i) total += descs_host[i].nbytes;
-  DescArray da{};
-  for (int off = 0; off < n; off += kMaxBatch) {
-    da.n = std::min(n - off, kMaxBatch);
-    for (int i = 0; i < da.n; ++i) da.d[i] = descs_host[off + i];
-    hipLaunchKernelGGL(batched_sum_kernel_bf16, dim3(GridFor(total / 16)), dim3(kBlock), 0, s,
-                       da);
-  }
+  LaunchLegacy(batched_sum_kernel_bf16, descs_host, n, s, tile_cap);
+}
+
+// the sparse kernels' grid: up to 16384 blocks, fewer under a grid_cap
+static int SparseGrid(size_t work_items, int grid_cap) {
+  return CapGrid(GridFor(work_items, 16384), grid_cap);
 }
 
 void SparseGatherF32(const float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                      float* out, hipStream_t s, int key_shift, uint64_t row_base,
-                     uint64_t table_rows) {
+                     uint64_t table_rows, int grid_cap) {
   if (row_len % 4 == 0) {
-    hipLaunchKernelGGL(gather_rows_f32, dim3(GridFor(nrows * (row_len / 4), 16384)), dim3(kBlock),
-                       0, s, reinterpret_cast<const float4*>(table), rows_dev, nrows, row_len / 4,
-                       reinterpret_cast<float4*>(out), key_shift, row_base, table_rows);
+    hipLaunchKernelGGL(gather_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
+                       dim3(kBlock), 0, s, reinterpret_cast<const float4*>(table), rows_dev,
+                       nrows, row_len / 4, reinterpret_cast<float4*>(out), key_shift, row_base,
+                       table_rows);
   } else {
-    hipLaunchKernelGGL(gather_rows_scalar_f32, dim3(GridFor(nrows * row_len, 16384)), dim3(kBlock),
-                       0, s, table, rows_dev, nrows, row_len, out, key_shift, row_base, table_rows);
+    hipLaunchKernelGGL(gather_rows_scalar_f32, dim3(SparseGrid(nrows * row_len, grid_cap)),
+                       dim3(kBlock), 0, s, table, rows_dev, nrows, row_len, out, key_shift,
+                       row_base, table_rows);
   }
 }
 
 void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                             const float* src, hipStream_t s, int key_shift, uint64_t row_base,
-                            uint64_t table_rows) {
+                            uint64_t table_rows, int grid_cap) {
   if (row_len % 4 == 0) {
-    hipLaunchKernelGGL(scatter_assign_rows_f32, dim3(GridFor(nrows * (row_len / 4), 16384)),
+    hipLaunchKernelGGL(scatter_assign_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
                        dim3(kBlock), 0, s, reinterpret_cast<float4*>(table), rows_dev, nrows,
                        row_len / 4, reinterpret_cast<const float4*>(src), key_shift, row_base,
                        table_rows);
   } else {
-    hipLaunchKernelGGL(scatter_assign_rows_scalar_f32, dim3(GridFor(nrows * row_len, 16384)),
-                       dim3(kBlock), 0, s, table, rows_dev, nrows, row_len, src, key_shift,
-                       row_base, table_rows);
+    hipLaunchKernelGGL(scatter_assign_rows_scalar_f32,
+                       dim3(SparseGrid(nrows * row_len, grid_cap)), dim3(kBlock), 0, s, table,
+                       rows_dev, nrows, row_len, src, key_shift, row_base, table_rows);
   }
 }
 
 void SparseScatterAddF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                          const float* src, bool atomic, hipStream_t s, int key_shift,
-                         uint64_t row_base, uint64_t table_rows) {
+                         uint64_t row_base, uint64_t table_rows, int grid_cap) {
   if (atomic || row_len % 4 != 0) {
-    hipLaunchKernelGGL(scatter_add_rows_atomic_f32, dim3(GridFor(nrows * row_len, 16384)),
+    hipLaunchKernelGGL(scatter_add_rows_atomic_f32, dim3(SparseGrid(nrows * row_len, grid_cap)),
                        dim3(kBlock), 0, s, table, rows_dev, nrows, row_len, src, key_shift,
                        row_base, table_rows);
   } else {
-    hipLaunchKernelGGL(scatter_add_rows_f32, dim3(GridFor(nrows * (row_len / 4), 16384)),
+    hipLaunchKernelGGL(scatter_add_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
                        dim3(kBlock), 0, s, reinterpret_cast<float4*>(table), rows_dev, nrows,
                        row_len / 4, reinterpret_cast<const float4*>(src), key_shift, row_base,
                        table_rows);

@@ -865,10 +865,13 @@ PYBIND11_MODULE(_core, m) {
   }, py::arg("keys"), py::arg("nthreads") = 4);
 
   // raw kernel entry points (synchronous; for numerics tests)
-  m.def("k_dense_assign", [](uintptr_t dst, uintptr_t src, size_t nbytes) {
-    kern::DenseAssign(reinterpret_cast<void*>(dst), reinterpret_cast<void*>(src), nbytes, nullptr);
-    gpu::DeviceSync(-1);
-  });
+  m.def("k_dense_assign",
+        [](uintptr_t dst, uintptr_t src, size_t nbytes, int grid_cap) {
+          kern::DenseAssign(reinterpret_cast<void*>(dst), reinterpret_cast<void*>(src), nbytes,
+                            nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("grid_cap") = 0);
   m.def("k_dense_assign2",
         [](uintptr_t dst0, uintptr_t dst1, uintptr_t src, size_t nbytes, int grid_cap) {
           kern::DenseAssign2(reinterpret_cast<void*>(dst0), reinterpret_cast<void*>(dst1),
@@ -897,30 +900,83 @@ PYBIND11_MODULE(_core, m) {
           gpu::DeviceSync(-1);
         },
         py::arg("segs"), py::arg("tile_cap") = 0);
-  m.def("k_dense_sum_f32", [](uintptr_t dst, uintptr_t src, size_t n) {
-    kern::DenseSumF32(reinterpret_cast<float*>(dst), reinterpret_cast<float*>(src), n, nullptr);
-    gpu::DeviceSync(-1);
-  });
-  m.def("k_dense_sum_bf16", [](uintptr_t dst, uintptr_t src, size_t n) {
-    kern::DenseSumBf16(reinterpret_cast<uint16_t*>(dst), reinterpret_cast<uint16_t*>(src), n,
-                       nullptr);
-    gpu::DeviceSync(-1);
-  });
+  m.def("k_dense_sum_f32",
+        [](uintptr_t dst, uintptr_t src, size_t n, int grid_cap) {
+          kern::DenseSumF32(reinterpret_cast<float*>(dst), reinterpret_cast<float*>(src), n,
+                            nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("dst"), py::arg("src"), py::arg("n"), py::arg("grid_cap") = 0);
+  m.def("k_dense_sum_bf16",
+        [](uintptr_t dst, uintptr_t src, size_t n, int grid_cap) {
+          kern::DenseSumBf16(reinterpret_cast<uint16_t*>(dst), reinterpret_cast<uint16_t*>(src), n,
+                             nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("dst"), py::arg("src"), py::arg("n"), py::arg("grid_cap") = 0);
+  // batched (dst, src, nbytes) segments; the launcher follows
+  // XPS_BALANCED_BATCH like the handlers' multi-key path
+  using Seg = std::tuple<uintptr_t, uintptr_t, size_t>;
+  using BatchedFn = void (*)(const kern::CopyDesc*, int, hipStream_t, int);
+  auto batched = [](const char* name, BatchedFn launch) {
+    return [name, launch](const std::vector<Seg>& segs, int tile_cap) {
+      std::vector<kern::CopyDesc> v;
+      for (auto& t : segs) {
+        if ((std::get<0>(t) | std::get<1>(t) | std::get<2>(t)) & 15u) {
+          throw std::invalid_argument(std::string(name) + ": segment " +
+                                      std::to_string(v.size()) +
+                                      " is misaligned or not a 16 B multiple");
+        }
+        v.push_back(kern::CopyDesc{reinterpret_cast<void*>(std::get<0>(t)),
+                                   reinterpret_cast<const void*>(std::get<1>(t)),
+                                   std::get<2>(t)});
+      }
+      launch(v.data(), static_cast<int>(v.size()), nullptr, tile_cap);
+      gpu::DeviceSync(-1);
+    };
+  };
+  m.def("k_batched_assign", batched("k_batched_assign", kern::BatchedAssign), py::arg("segs"),
+        py::arg("tile_cap") = 0);
+  m.def("k_batched_sum_f32", batched("k_batched_sum_f32", kern::BatchedSumF32), py::arg("segs"),
+        py::arg("tile_cap") = 0);
+  m.def("k_batched_sum_bf16", batched("k_batched_sum_bf16", kern::BatchedSumBf16),
+        py::arg("segs"), py::arg("tile_cap") = 0);
   m.def("k_sparse_gather_f32",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out) {
+        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
+           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
           kern::SparseGatherF32(reinterpret_cast<float*>(table),
                                 reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                reinterpret_cast<float*>(out), nullptr);
+                                reinterpret_cast<float*>(out), nullptr, key_shift, row_base,
+                                table_rows, grid_cap);
           gpu::DeviceSync(-1);
-        });
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
   m.def("k_sparse_scatter_add_f32",
         [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-           bool atomic) {
+           bool atomic, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
           kern::SparseScatterAddF32(reinterpret_cast<float*>(table),
                                     reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                    reinterpret_cast<float*>(src), atomic, nullptr);
+                                    reinterpret_cast<float*>(src), atomic, nullptr, key_shift,
+                                    row_base, table_rows, grid_cap);
           gpu::DeviceSync(-1);
-        });
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("atomic"), py::arg("key_shift") = 0, py::arg("row_base") = 0,
+        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("k_sparse_scatter_assign_f32",
+        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
+           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseScatterAssignF32(reinterpret_cast<float*>(table),
+                                       reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                       reinterpret_cast<float*>(src), nullptr, key_shift,
+                                       row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
 
   py::class_<PySimpleApp>(m, "SimpleApp")
       .def(py::init<const std::string&, int, int>(), py::arg("role"), py::arg("app_id") = 10,
