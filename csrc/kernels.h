@@ -77,6 +77,18 @@ struct CopyDesc {
   const void* src;
   size_t nbytes;  // must be 16B-multiples for the batched kernels
 };
+// The batched kernels' contract for a segment list: every dst and src
+// 16 B-aligned, every length a 16 B multiple. A list that fails it goes
+// through the per-segment launchers, which take any skew.
+inline bool BatchAligned(const CopyDesc* descs, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    if ((reinterpret_cast<uintptr_t>(descs[i].dst) | reinterpret_cast<uintptr_t>(descs[i].src) |
+         descs[i].nbytes) & 15u) {
+      return false;
+    }
+  }
+  return true;
+}
 // Segments may be empty. tile_cap > 0 caps the number of blocks (tests):
 // on the balanced path the tile grows and a block sweeps several strides
 // of it, on the XPS_BALANCED_BATCH=0 path the grid-stride grid shrinks.

@@ -280,6 +280,10 @@ class KVWorker : public SimpleApp {
         // semantics only (sum needs the server's accumulate kernel).
         {
           std::lock_guard<std::mutex> lk(mu_);
+          // A multi-key push may grow (and so replace) any entry it names,
+          // and its ack carries no advert: adverts of this server learned
+          // from requests sent before it are not cached any more.
+          if (s.keys.size() > 1) advert_floor_[msg.meta.recver] = ts;
           auto nit = entry_cache_.find(msg.meta.recver);
           if (nit != entry_cache_.end() && !nit->second.empty()) {
             if (!pull && s.keys.size() == 1 && cmd != kCmdSum && s.vals.on_device()) {
@@ -293,14 +297,27 @@ class KVWorker : public SimpleApp {
                 msg.meta.option |= kOptEntryPush;
                 it->second.one_sided = true;
               } else if (it != nit->second.end()) {
-                it->second.one_sided = false;  // normal push re-orders via server
+                // another length (the push may replace the entry) or another
+                // server process: the advert is dead; this push's ack
+                // brings the live one
+                nit->second.erase(it);
               }
             } else {
               // normal / multi-key push: any contained cached key loses
-              // its one-sided ordering chain
+              // its one-sided ordering chain, and its advert too where the
+              // push may replace the entry (the advert must not outlive
+              // the buffer it names: a later push of the old length would
+              // go one-sided into the retired buffer and never reach the
+              // store)
               for (size_t ki = 0; ki < s.keys.size(); ++ki) {
                 auto it = nit->second.find(s.keys[ki]);
-                if (it != nit->second.end()) it->second.one_sided = false;
+                if (it == nit->second.end()) continue;
+                if (s.keys.size() > 1 ||
+                    it->second.len != static_cast<int64_t>(s.vals.nbytes())) {
+                  nit->second.erase(it);
+                } else {
+                  it->second.one_sided = false;
+                }
               }
             }
           }
@@ -441,7 +458,8 @@ class KVWorker : public SimpleApp {
         // a fused push+pull response advertises the entry too (offset in
         // entry_addr: addr still names the in-place destination)
         if (msg.meta.push && (msg.meta.option & kOptEntryAddr)) {
-          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.entry_addr, msg.meta.val_len);
+          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.entry_addr, msg.meta.val_len,
+                           ts);
         }
         auto& got = recv_kvs_[ts];
         got.push_back(RecvSlice{kvs, msg.meta.option, msg.meta.val_len});
@@ -450,7 +468,7 @@ class KVWorker : public SimpleApp {
         // a push ACK may advertise the server's entry offset for this
         // key: cache it so later assign pushes go one-sided
         if (msg.meta.option & kOptEntryAddr) {
-          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.addr, msg.meta.val_len);
+          CacheEntryLocked(msg.meta.sender, msg.meta.key, msg.meta.addr, msg.meta.val_len, ts);
         }
         int n = ++push_acks_[ts];
         last = n >= expected_[ts];
@@ -568,10 +586,16 @@ class KVWorker : public SimpleApp {
   std::unordered_map<int, std::unordered_map<Key, EntryRec>> entry_cache_;
 
   // (re)learn an advert: the server applied this request itself, so the
-  // key's one-sided chain restarts (one_sided = false)
-  void CacheEntryLocked(int server_id, Key key, uint64_t off, int64_t len) {
+  // key's one-sided chain restarts (one_sided = false). ts is the
+  // request the advert answers: one sent before the server's latest
+  // multi-key push names an entry that push may have replaced since.
+  void CacheEntryLocked(int server_id, Key key, uint64_t off, int64_t len, int ts) {
+    auto fit = advert_floor_.find(server_id);
+    if (fit != advert_floor_.end() && ts < fit->second) return;
     entry_cache_[server_id][key] = EntryRec{off, len, po_->van()->GetNode(server_id).shm_uid};
   }
+  // server node id -> timestamp of the latest multi-key push sent to it
+  std::unordered_map<int, int> advert_floor_;
 
   const EntryRec* FindEntryLocked(int server_id, Key key) const {
     auto nit = entry_cache_.find(server_id);

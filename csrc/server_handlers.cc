@@ -53,6 +53,14 @@ static void EventFree(Postoffice* po, hipEvent_t ev) {
 
 // ------------------------------------------------------------------ dense
 
+// Does the van stage this pull response's device vals through host memory
+// (no in-place HBM destination: none advertised, or a host-pool one)? Its
+// device-to-host copy is stream-unaware, so the handler drains its stream
+// first.
+static bool StagedOnHost(int option) {
+  return !(option & kOptPullAddr) || (option & kOptHostAddr);
+}
+
 static EventRef MakeEventRef(Postoffice* po, hipStream_t s) {
   hipEvent_t ev = EventAlloc(po);
   XPS_HIP_CHECK(hipEventRecord(ev, s));
@@ -96,6 +104,17 @@ GpuDenseHandler::~GpuDenseHandler() = default;
 
 void GpuDenseHandler::OrderAfter(Entry* e, hipStream_t s) {
   if (e->last_ev) XPS_HIP_CHECK(hipStreamWaitEvent(s, e->last_ev.get(), 0));
+}
+
+void GpuDenseHandler::Replace(Entry* e, size_t len) {
+  // retire (never free) a smaller buffer: workers may hold its offset in
+  // their one-sided entry caches — a stale write must land in
+  // dead-but-owned memory, not a reused pool region
+  if (!e->buf.empty()) e->retired.push_back(e->buf);
+  e->buf = HbmPool::Get()->AllocArray(len);
+  // zero before publishing: another peer's stream may accumulate into
+  // this entry concurrently with our first push
+  XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
 }
 
 hipStream_t GpuDenseHandler::Stream(int sender) {
@@ -162,11 +181,7 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
     // allocate / retire / zero / grow exactly as HandlePush does
     std::lock_guard<std::mutex> lk(mu_);
     e = &store_[kvs.keys[0]];
-    if (e->buf.size() < len) {
-      if (!e->buf.empty()) e->retired.push_back(e->buf);
-      e->buf = HbmPool::Get()->AllocArray(len);
-      XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
-    }
+    if (e->buf.size() < len) Replace(e, len);
   }
   // a LARGER entry keeps its tail: the pull would return more than was
   // pushed — that is the two-step path's business
@@ -268,16 +283,14 @@ void GpuDenseHandler::HandleReducePush(const KVMeta& req, const KVPairs<float>& 
   std::vector<kern::CopyDesc> descs;
   descs.reserve(n);
   size_t off = 0;
-  bool aligned = true;
   for (size_t i = 0; i < n; ++i) {
     size_t len = g->lens[i];
     Entry* e = g->ents[i];
     if (e->buf.size() < len) e->buf = HbmPool::Get()->AllocArray(len);
     descs.push_back({e->buf.data(), reinterpret_cast<const char*>(kvs.vals.data()) + off, len});
-    aligned = aligned && (len % 16 == 0);
     off += len;
   }
-  if (aligned) {
+  if (kern::BatchAligned(descs.data(), n)) {
     if (first) {
       kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
     } else {
@@ -331,7 +344,6 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
     descs.reserve(n);
     ents.reserve(n);
     size_t boff = 0;
-    bool aligned = true;
     for (size_t i = 0; i < n; ++i) {
       size_t len = kvs.lens.empty() ? kvs.vals.nbytes() / n
                                     : static_cast<size_t>(kvs.lens[i]) * sizeof(float);
@@ -339,18 +351,14 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
       {
         std::lock_guard<std::mutex> lk(mu_);
         e = &store_[kvs.keys[i]];
-        if (e->buf.size() < len) {
-          e->buf = HbmPool::Get()->AllocArray(len);
-          XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
-        }
+        if (e->buf.size() < len) Replace(e, len);
       }
       ents.push_back(e);
       descs.push_back({e->buf.data(),
                        reinterpret_cast<const char*>(kvs.vals.data()) + boff, len});
-      aligned = aligned && (len % 16 == 0) && (boff % 16 == 0);
       boff += len;
     }
-    if (aligned) {
+    if (kern::BatchAligned(descs.data(), n)) {
       for (Entry* e : ents) OrderAfter(e, stream);
       if (sum_all) {
         BatchedSum(descs.data(), static_cast<int>(n), stream);
@@ -377,16 +385,7 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
     {
       std::lock_guard<std::mutex> lk(mu_);
       e = &store_[kvs.keys[i]];
-      if (e->buf.size() < len) {
-        // retire (never free) a smaller buffer: workers may hold its
-        // offset in their one-sided entry caches — a stale write must
-        // land in dead-but-owned memory, not a reused pool region
-        if (!e->buf.empty()) e->retired.push_back(e->buf);
-        e->buf = HbmPool::Get()->AllocArray(len);
-        // zero before publishing: another peer's stream may accumulate
-        // into this entry concurrently with our first push
-        XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
-      }
+      if (e->buf.size() < len) Replace(e, len);
     }
     last_e = e;
     bool sum = sum_all;
@@ -458,8 +457,9 @@ void GpuDenseHandler::RespondPull(const KVMeta& req, Group* g, KVServer<float>* 
   for (size_t i = 0; i < n; ++i) lens[i] = static_cast<int>(g->lens[i] / sizeof(float));
   bool responded = false;
   // fast path: write the whole group straight into the requester's
-  // advertised pool destination (one batched kernel, meta-only response)
-  if (req.option & kOptPullAddr) {
+  // advertised HBM pool destination (one batched kernel, meta-only
+  // response); kOptHostAddr names an offset in the host pool instead
+  if ((req.option & kOptPullAddr) && !(req.option & kOptHostAddr)) {
     if (auto* plane = ThePlane(po_)) {
       std::vector<kern::CopyDesc> descs;
       descs.reserve(n);
@@ -468,12 +468,13 @@ void GpuDenseHandler::RespondPull(const KVMeta& req, Group* g, KVServer<float>* 
       for (size_t i = 0; i < n && ok; ++i) {
         size_t len = g->lens[i];
         char* dst = plane->PeerDst(req.sender, req.addr + off, len);
-        ok = dst != nullptr && len % 16 == 0;
+        ok = dst != nullptr;
         if (ok) {
           descs.push_back({dst, g->ents[i]->buf.data(), len});
           off += len;
         }
       }
+      ok = ok && kern::BatchAligned(descs.data(), descs.size());
       if (ok) {
         kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
         KVMeta r2 = req;
@@ -499,20 +500,18 @@ void GpuDenseHandler::RespondPull(const KVMeta& req, Group* g, KVServer<float>* 
       std::vector<kern::CopyDesc> descs;
       descs.reserve(n);
       size_t off = 0;
-      bool aligned = true;
       for (size_t i = 0; i < n; ++i) {
         descs.push_back({tmp.data() + off, g->ents[i]->buf.data(), g->lens[i]});
-        aligned = aligned && (g->lens[i] % 16 == 0) && (off % 16 == 0);
         off += g->lens[i];
       }
-      if (aligned) {
+      if (kern::BatchAligned(descs.data(), n)) {
         kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
       } else {
         for (auto& d : descs) kern::DenseAssign(d.dst, d.src, d.nbytes, stream);
       }
       res.vals = SArray<float>::View(tmp);  // plane keeps it alive until sent
     }
-    if (!(req.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+    if (StagedOnHost(req.option)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
     KVMeta r = req;
     r.option |= kOptPullLane;  // ordering prepared on the pull lane
     server->Response(r, res);  // plane enqueues the in-place read on `stream`
@@ -572,8 +571,11 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
   bool chain = NeedChain(req.sender);
   // multi-key pull with an in-place destination: batched copy of every
   // store entry straight into the requester's mapped pool (no staging
-  // buffer, meta-only response)
-  if (n > 1 && (req.option & kOptPullAddr)) {
+  // buffer, meta-only response). The destination is an HBM one
+  // (kOptHostAddr names an offset in the host pool) and holds every entry:
+  // entries that grew since the worker sized its buffer go through the
+  // staging branch below, which strips kOptPullAddr for them.
+  if (n > 1 && (req.option & kOptPullAddr) && !(req.option & kOptHostAddr)) {
     if (auto* plane = ThePlane(po_)) {
       std::vector<kern::CopyDesc> descs;
       std::vector<Entry*> ents;
@@ -587,7 +589,7 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
           XPS_CHECK(it != store_.end()) << "pull of unknown key " << kvs.keys[i];
           size_t len = it->second.buf.size();
           char* dst = plane->PeerDst(req.sender, req.addr + off, len);
-          ok = dst != nullptr && len % 16 == 0 && off % 16 == 0;
+          ok = dst != nullptr;
           if (ok) {
             ents.push_back(&it->second);
             descs.push_back({dst, it->second.buf.data(), len});
@@ -596,6 +598,8 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
           }
         }
       }
+      ok = ok && kern::BatchAligned(descs.data(), descs.size()) &&
+           !(req.val_len > 0 && off > static_cast<uint64_t>(req.val_len));
       if (ok) {
         for (Entry* e : ents) OrderAfter(e, stream);
         kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
@@ -654,13 +658,11 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
     size_t off = 0;
     std::vector<kern::CopyDesc> descs;
     descs.reserve(n);
-    bool aligned = true;
     for (size_t i = 0; i < n; ++i) {
       descs.push_back({tmp.data() + off, entries[i].data(), entries[i].size()});
-      aligned = aligned && (entries[i].size() % 16 == 0) && (off % 16 == 0);
       off += entries[i].size();
     }
-    if (aligned) {
+    if (kern::BatchAligned(descs.data(), n)) {
       kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
     } else {
       for (auto& d : descs) kern::DenseAssign(d.dst, d.src, d.nbytes, stream);
@@ -677,9 +679,9 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
       static_cast<int64_t>(res.vals.nbytes()) > req.val_len && req.val_len > 0) {
     r.option &= ~kOptPullAddr;
   }
-  // TCP fallback (no in-place destination): the staging D2H copy below in
-  // the van is stream-unaware — drain our stream first
-  if (!(r.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+  // TCP fallback (no in-place HBM destination): the staging D2H copy below
+  // in the van is stream-unaware — drain our stream first
+  if (StagedOnHost(r.option)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
   r.option |= kOptPullLane;  // ordering prepared on the pull lane
   server->Response(r, res);  // plane enqueues the in-place read on `stream`
   if (chain) {
@@ -729,7 +731,7 @@ void GpuDenseHandler::Load(const std::string& path) {
     host.resize(len);
     XPS_CHECK_EQ(fread(host.data(), 1, len, f), len);
     auto& e = store_[key];
-    if (e.buf.size() < len) e.buf = HbmPool::Get()->AllocArray(len);
+    if (e.buf.size() < len) Replace(&e, len);
     XPS_HIP_CHECK(hipMemcpy(e.buf.data(), host.data(), len, hipMemcpyHostToDevice));
   }
   fclose(f);
@@ -747,7 +749,13 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
   atomic_ = po_->num_workers() > 1;
   if (key_shift_ > 0) {
     int rank = po_->my_rank();
-    row_base_ = po_->GetServerKeyRanges()[rank].begin >> key_shift_;
+    // the first row whose key (row << key_shift) lies in our range. Range
+    // begins are multiples of (2^64 - 1) / num_servers, which fall one
+    // short of the row boundary for a power-of-two split: round up, or
+    // every local row sits one too high and the shard's last row is lost.
+    uint64_t begin = po_->GetServerKeyRanges()[rank].begin;
+    uint64_t low = (1ull << key_shift_) - 1;
+    row_base_ = (begin >> key_shift_) + ((begin & low) ? 1 : 0);
   }
   XPS_HIP_CHECK(hipSetDevice(pool->device()));
   table_ = pool->AllocArray(rows * row_len * sizeof(float));

@@ -73,8 +73,9 @@ class GpuDenseHandler {
     EventRef last_ev;
     // superseded (smaller) buffers, kept alive forever: workers may
     // still hold their offsets in one-sided entry caches; stale writes
-    // must hit dead-but-owned memory (they self-heal — the mismatched
-    // length makes the worker fall back and re-learn the new offset)
+    // must hit dead-but-owned memory. Workers drop an advert when they
+    // send the key in a multi-key push or at another length (KVWorker::
+    // Send), so such a write needs a push that raced the replacing one.
     std::vector<SArray<char>> retired;
   };
 
@@ -119,6 +120,9 @@ class GpuDenseHandler {
   // peer's lanes actually split = cross-device)
   bool NeedChain(int sender);
   void OrderAfter(Entry* e, hipStream_t s);  // wait the entry's last_ev
+  // give a too-small entry a zeroed buffer of exactly len bytes; the old
+  // one is retired, never freed (mu_ held)
+  static void Replace(Entry* e, size_t len);
 
   // dtype-dispatched accumulate (nbytes, not elements)
   void SumKernel(void* dst, const void* src, size_t nbytes, hipStream_t s);
