@@ -76,6 +76,15 @@ dualwritebench: build/csrc/kernels.hip.o build/bench_dualwrite.o
 	$(HIPCC) $(CPPBENCH_LD) build/bench_dualwrite.o build/csrc/kernels.hip.o \
 	    -o build/bench_dualwrite
 
+# one-process timing of the MXFP8 kernels against the copy kernel at equal
+# traffic (links kernels.hip and mxfp8.hip only): build/bench_mxfp8
+build/bench_mxfp8.o: examples/cpp/bench_mxfp8.hip csrc/*.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_mxfp8.hip -o build/bench_mxfp8.o
+mxfp8bench: build/csrc/kernels.hip.o build/csrc/mxfp8.hip.o build/bench_mxfp8.o
+	$(HIPCC) $(CPPBENCH_LD) build/bench_mxfp8.o build/csrc/kernels.hip.o \
+	    build/csrc/mxfp8.hip.o -o build/bench_mxfp8
+
 # self-contained lint gate (reference parity: tests/lint.py + make lint)
 lint:
 	python3 scripts/lint.py
@@ -85,4 +94,4 @@ lint:
 check: all lint
 	python3 -m pytest tests -q -m "not gpu"
 
-.PHONY: all clean cppbench dualwritebench lint check
+.PHONY: all clean cppbench dualwritebench mxfp8bench lint check

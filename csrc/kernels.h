@@ -45,8 +45,6 @@ void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s, int grid
 // bandwidth-bound dense path)
 void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s, int grid_cap = 0);
 void BatchedSumBf16(const struct CopyDesc* descs_host, int n, hipStream_t s, int tile_cap = 0);
-// dst[i] += sum_j srcs[j][i], up to 8 sources in one pass (one read of
-// dst, one write — HBM-optimal multi-worker reduction)
 // Sparse ops: local row index = (rows[r] >> key_shift) - row_base, so a
 // server can index its local table shard from globally-sharded keys
 // (key = global_row << key_shift spreads rows over the PS key space).
@@ -104,6 +102,39 @@ void BatchedSumF32(const CopyDesc* descs_host, int n, hipStream_t s, int tile_ca
 // several tile iterations per block on small inputs).
 static_assert(kMaxBatch2 == kMaxBatch, "Seg2 batches use the batched kernels' segment limit");
 void BatchedAssign2(const Seg2* segs_host, int n, hipStream_t s, int tile_cap = 0);
+
+// MXFP8 payloads (mxfp8.h: 512 fp32 elements per 528-byte superblock, one
+// E8M0 scale byte per 32 elements, OCP e4m3fn codes; kernels in mxfp8.hip).
+// Every packed pointer must be 16 B-aligned and every packed length a
+// multiple of 528, else std::invalid_argument and nothing is launched.
+// fp32 pointers may sit at any 4-byte offset; off a 16 B boundary they are
+// read and written element-wise. grid_cap / tile_cap > 0 cap the grid
+// (tests).
+// packed = Q(src[0, n)): any n, writes MxPackedBytes(n) bytes, the last
+// superblock zero-filled past n
+void MxQuantize(const float* src, size_t n, void* packed, hipStream_t s, int grid_cap = 0);
+// dst[0, n) = D(packed) * alpha: writes exactly n floats
+void MxDequantize(const void* packed, size_t n, float* dst, float alpha, hipStream_t s,
+                  int grid_cap = 0);
+// acc (= | +=) D(packed), one IEEE add per element; acc holds
+// nbytes / 528 * 512 floats
+void MxAccumulate(float* acc, const void* packed, size_t nbytes, bool assign, hipStream_t s,
+                  int grid_cap = 0);
+// packed_out = Q((acc or 0) + D(packed_in)); acc is only read
+void MxFinish(const float* acc_or_null, const void* packed_in, void* packed_out, size_t nbytes,
+              hipStream_t s, int grid_cap = 0);
+// The same over segments, one launch per kMaxBatch of them; segments may
+// be empty and must not overlap each other. Accumulate ignores out, finish
+// takes a null acc as zeros. Both return the number of launches.
+struct MxSeg {
+  float* acc;
+  const void* in;
+  void* out;
+  size_t nbytes;  // packed bytes of in (and out)
+};
+int BatchedMxAccumulate(const MxSeg* segs_host, int n, bool assign, hipStream_t s,
+                        int tile_cap = 0);
+int BatchedMxFinish(const MxSeg* segs_host, int n, hipStream_t s, int tile_cap = 0);
 
 }  // namespace kern
 }  // namespace xps

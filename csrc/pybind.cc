@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "kv_app.h"
 #include "kv_utils.h"
+#include "mxfp8.h"
 #include "ps.h"
 #include "server_handlers.h"
 #include "shm_ring.h"
@@ -315,7 +316,12 @@ class PyKVServer {
     DenseMode m = mode == "sum" ? DenseMode::kSum
                   : mode == "reduce" ? DenseMode::kReduce
                                      : DenseMode::kAssign;
-    DenseDtype d = dtype == "bf16" ? DenseDtype::kBf16 : DenseDtype::kF32;
+    DenseDtype d = dtype == "bf16"    ? DenseDtype::kBf16
+                   : dtype == "mxfp8" ? DenseDtype::kMxfp8
+                                      : DenseDtype::kF32;
+    if (d == DenseDtype::kMxfp8 && m != DenseMode::kReduce) {
+      throw py::value_error("dtype=\"mxfp8\" needs mode=\"reduce\" (got mode=\"" + mode + "\")");
+    }
     auto h = std::make_shared<GpuDenseHandler>(s_.postoffice(), m, d);
     dense_ = h;
     s_.set_request_handle([h](const KVMeta& m2, const KVPairs<float>& kvs, KVServer<float>* srv) {
@@ -576,6 +582,29 @@ PYBIND11_MODULE(_core, m) {
   // fused dual-write launches (server fast path + worker one-sided path)
   m.def("fused_assign_count", []() { return g_fused_assign.load(); });
   m.def("fused_assign_launches", []() { return g_fused_launches.load(); });
+  // MXFP8 accumulate / finish launches of the reduce-mode dense handler
+  m.def("mxfp8_launches", []() { return g_mx_launches.load(); });
+  // the MXFP8 format's host reference (mxfp8.h; no GPU involved)
+  m.def("mxfp8_packed_nbytes", [](size_t n) { return mx::MxPackedBytes(n); }, py::arg("n"));
+  m.def("mxfp8_quantize_host",
+        [](py::array_t<float, py::array::c_style | py::array::forcecast> src) {
+          size_t n = static_cast<size_t>(src.size());
+          py::array_t<uint8_t> out(mx::MxPackedBytes(n));
+          mx::MxQuantizeHost(src.data(), n, out.mutable_data());
+          return out;
+        },
+        py::arg("src"));
+  m.def("mxfp8_dequantize_host",
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, size_t n,
+           float alpha) {
+          if (static_cast<size_t>(packed.size()) < mx::MxPackedBytes(n)) {
+            throw std::invalid_argument("mxfp8_dequantize_host: packed is shorter than n elements");
+          }
+          py::array_t<float> out(n);
+          mx::MxDequantizeHost(packed.data(), n, out.mutable_data(), alpha);
+          return out;
+        },
+        py::arg("packed"), py::arg("n"), py::arg("alpha") = 1.0f);
   // the coalescer's admit-or-flush decision (pure host code): segments
   // are (dst0, dst1, src, nbytes) address tuples, nothing is dereferenced.
   // Returns "admit", "flush" or "reject".
@@ -940,6 +969,72 @@ PYBIND11_MODULE(_core, m) {
   m.def("k_batched_sum_f32", batched("k_batched_sum_f32", kern::BatchedSumF32), py::arg("segs"),
         py::arg("tile_cap") = 0);
   m.def("k_batched_sum_bf16", batched("k_batched_sum_bf16", kern::BatchedSumBf16),
+        py::arg("segs"), py::arg("tile_cap") = 0);
+  // MXFP8 kernels (mxfp8.hip); packed pointers 16 B-aligned, packed
+  // lengths multiples of 528, else ValueError before any launch
+  m.def("k_mx_quantize",
+        [](uintptr_t src, size_t n, uintptr_t packed, int grid_cap) {
+          kern::MxQuantize(reinterpret_cast<const float*>(src), n,
+                           reinterpret_cast<void*>(packed), nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("src"), py::arg("n"), py::arg("packed"), py::arg("grid_cap") = 0);
+  m.def("k_mx_dequantize",
+        [](uintptr_t packed, size_t n, uintptr_t dst, float alpha, int grid_cap) {
+          kern::MxDequantize(reinterpret_cast<const void*>(packed), n,
+                             reinterpret_cast<float*>(dst), alpha, nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("packed"), py::arg("n"), py::arg("dst"), py::arg("alpha") = 1.0f,
+        py::arg("grid_cap") = 0);
+  m.def("k_mx_accumulate",
+        [](uintptr_t acc, uintptr_t packed, size_t nbytes, bool assign, int grid_cap) {
+          kern::MxAccumulate(reinterpret_cast<float*>(acc), reinterpret_cast<const void*>(packed),
+                             nbytes, assign, nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("acc"), py::arg("packed"), py::arg("nbytes"), py::arg("assign"),
+        py::arg("grid_cap") = 0);
+  m.def("k_mx_finish",
+        [](uintptr_t acc, uintptr_t packed_in, uintptr_t packed_out, size_t nbytes,
+           int grid_cap) {
+          kern::MxFinish(reinterpret_cast<const float*>(acc),
+                         reinterpret_cast<const void*>(packed_in),
+                         reinterpret_cast<void*>(packed_out), nbytes, nullptr, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("acc"), py::arg("packed_in"), py::arg("packed_out"), py::arg("nbytes"),
+        py::arg("grid_cap") = 0);
+  // batched (acc, packed_in, packed_out, nbytes) segments; acc = 0 is the
+  // finish kernel's "no accumulator", accumulate ignores packed_out.
+  // Returns the number of launches.
+  using MxSegT = std::tuple<uintptr_t, uintptr_t, uintptr_t, size_t>;
+  auto mx_segs = [](const std::vector<MxSegT>& segs) {
+    std::vector<kern::MxSeg> v;
+    for (auto& t : segs) {
+      v.push_back(kern::MxSeg{reinterpret_cast<float*>(std::get<0>(t)),
+                              reinterpret_cast<const void*>(std::get<1>(t)),
+                              reinterpret_cast<void*>(std::get<2>(t)), std::get<3>(t)});
+    }
+    return v;
+  };
+  m.def("k_batched_mx_accumulate",
+        [mx_segs](const std::vector<MxSegT>& segs, bool assign, int tile_cap) {
+          auto v = mx_segs(segs);
+          int launches = kern::BatchedMxAccumulate(v.data(), static_cast<int>(v.size()), assign,
+                                                   nullptr, tile_cap);
+          gpu::DeviceSync(-1);
+          return launches;
+        },
+        py::arg("segs"), py::arg("assign"), py::arg("tile_cap") = 0);
+  m.def("k_batched_mx_finish",
+        [mx_segs](const std::vector<MxSegT>& segs, int tile_cap) {
+          auto v = mx_segs(segs);
+          int launches = kern::BatchedMxFinish(v.data(), static_cast<int>(v.size()), nullptr,
+                                               tile_cap);
+          gpu::DeviceSync(-1);
+          return launches;
+        },
         py::arg("segs"), py::arg("tile_cap") = 0);
   m.def("k_sparse_gather_f32",
         [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,

@@ -3,8 +3,11 @@
 #include "gpu_plane.h"
 #include "hip_pool.h"
 #include "kernels.h"
+#include "mxfp8.h"
 
 namespace xps {
+
+std::atomic<uint64_t> g_mx_launches{0};
 
 #define XPS_HIP_CHECK(cmd)                                                            \
   do {                                                                                \
@@ -70,12 +73,15 @@ static EventRef MakeEventRef(Postoffice* po, hipStream_t s) {
 GpuDenseHandler::GpuDenseHandler(Postoffice* po, DenseMode mode, DenseDtype dtype)
     : po_(po), mode_(mode), dtype_(dtype) {
   XPS_CHECK(HbmPool::Get()->initialized()) << "GpuDenseHandler needs the HBM pool";
+  XPS_CHECK(dtype_ != DenseDtype::kMxfp8 || mode_ == DenseMode::kReduce)
+      << "mxfp8 payloads exist in reduce mode only";
   num_workers_ = std::max(1, po_->num_workers());
   // >1 workers: same-key kernels land on different peers' streams
   chain_ = num_workers_ > 1;
 }
 
 void GpuDenseHandler::SumKernel(void* dst, const void* src, size_t nbytes, hipStream_t s) {
+  XPS_CHECK(dtype_ != DenseDtype::kMxfp8) << "mxfp8 has no in-place sum";
   if (dtype_ == DenseDtype::kBf16) {
     kern::DenseSumBf16(static_cast<uint16_t*>(dst), static_cast<const uint16_t*>(src),
                        nbytes / 2, s);
@@ -85,6 +91,7 @@ void GpuDenseHandler::SumKernel(void* dst, const void* src, size_t nbytes, hipSt
 }
 
 void GpuDenseHandler::BatchedSum(const kern::CopyDesc* descs, int n, hipStream_t s) {
+  XPS_CHECK(dtype_ != DenseDtype::kMxfp8) << "mxfp8 has no in-place sum";
   if (dtype_ == DenseDtype::kBf16) {
     kern::BatchedSumBf16(descs, n, s);
   } else {
@@ -278,6 +285,11 @@ void GpuDenseHandler::HandleReducePush(const KVMeta& req, const KVPairs<float>& 
     }
     g->pull_guard.clear();
   }
+  if (dtype_ == DenseDtype::kMxfp8) {
+    ReducePushMx(g, kvs, stream);
+    FinishReducePush(req, g, server, stream);
+    return;
+  }
   // one batched kernel chain for the whole key-set (3 launches for 169
   // rn50 buckets at kMaxBatch=64), one event per push
   std::vector<kern::CopyDesc> descs;
@@ -305,6 +317,47 @@ void GpuDenseHandler::HandleReducePush(const KVMeta& req, const KVPairs<float>& 
       }
     }
   }
+  FinishReducePush(req, g, server, stream);
+}
+
+// MXFP8 round: the first push decodes into the fp32 accumulator, middle
+// pushes add to it, and the push that completes the round writes
+// Q(acc + D(push)) into the entries' packed buffers — each gradient is
+// rounded once at its worker and once here, however many workers add up.
+// With one worker the round is that last step alone.
+void GpuDenseHandler::ReducePushMx(Group* g, const KVPairs<float>& kvs, hipStream_t stream) {
+  size_t n = g->keys.size();
+  bool first = g->pushes == 0;
+  bool last = g->pushes + 1 >= num_workers_;
+  const char* vals = reinterpret_cast<const char*>(kvs.vals.data());
+  XPS_CHECK((reinterpret_cast<uintptr_t>(vals) & 15u) == 0)
+      << "mxfp8 push: vals must be 16 B-aligned";
+  std::vector<kern::MxSeg> segs;
+  segs.reserve(n);
+  size_t off = 0;
+  for (size_t i = 0; i < n; ++i) {
+    size_t len = g->lens[i];
+    XPS_CHECK(len % mx::kSuperBytes == 0)
+        << "mxfp8 push: key " << g->keys[i] << " has " << len
+        << " payload bytes, not a multiple of the 528-byte superblock";
+    Entry* e = g->ents[i];
+    if (e->buf.size() < len) e->buf = HbmPool::Get()->AllocArray(len);
+    XPS_CHECK((reinterpret_cast<uintptr_t>(e->buf.data()) & 15u) == 0)
+        << "mxfp8 push: the entry of key " << g->keys[i] << " is not 16 B-aligned";
+    size_t acc_len = len / mx::kSuperBytes * mx::kSuperF32Bytes;
+    if (!(first && last) && e->acc.size() < acc_len) e->acc = HbmPool::Get()->AllocArray(acc_len);
+    float* acc = first && last ? nullptr : reinterpret_cast<float*>(e->acc.data());
+    segs.push_back({acc, vals + off, e->buf.data(), len});
+    off += len;
+  }
+  XPS_CHECK_LE(off, kvs.vals.nbytes()) << "mxfp8 push: lens exceed the payload";
+  int launches = last ? kern::BatchedMxFinish(segs.data(), static_cast<int>(n), stream)
+                      : kern::BatchedMxAccumulate(segs.data(), static_cast<int>(n), first, stream);
+  g_mx_launches.fetch_add(static_cast<uint64_t>(launches), std::memory_order_relaxed);
+}
+
+void GpuDenseHandler::FinishReducePush(const KVMeta& req, Group* g, KVServer<float>* server,
+                                       hipStream_t stream) {
   g->pushes++;
   EventRef ev = MakeEventRef(po_, stream);
   g->round_events.push_back(ev);

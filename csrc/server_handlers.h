@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <memory>
 #include <set>
 #include <type_traits>
@@ -41,8 +42,13 @@ enum class DenseMode {
 
 // payload dtype of the accumulate kernels (the wire/pools are bytes;
 // bf16 halves bytes moved on the bandwidth-bound dense path). Assign
-// mode is dtype-agnostic byte copies either way.
-enum class DenseDtype { kF32, kBf16 };
+// mode is dtype-agnostic byte copies either way. kMxfp8 (mxfp8.h) exists
+// in reduce mode only: workers push and pull packed superblocks, the round
+// accumulates in fp32 and is rounded once more when it closes.
+enum class DenseDtype { kF32, kBf16, kMxfp8 };
+
+// launches of the MXFP8 accumulate / finish kernels by reduce-mode pushes
+extern std::atomic<uint64_t> g_mx_launches;
 
 class GpuDenseHandler {
  public:
@@ -77,6 +83,9 @@ class GpuDenseHandler {
     // send the key in a multi-key push or at another length (KVWorker::
     // Send), so such a write needs a push that raced the replacing one.
     std::vector<SArray<char>> retired;
+    // kMxfp8: the round's fp32 accumulator, 2048 bytes per superblock of
+    // buf, allocated by the first push that needs it; not checkpointed
+    SArray<char> acc;
   };
 
   // Reduce-mode round state, per KEY-SET: a worker's buckets for this
@@ -111,6 +120,11 @@ class GpuDenseHandler {
   // false = preconditions not met, nothing done
   bool TryFusedAssign(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void HandleReducePush(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
+  // kMxfp8: this push's accumulate or finish launches for the whole key-set
+  void ReducePushMx(Group* g, const KVPairs<float>& kvs, hipStream_t stream);
+  // count the push, publish its event, ack, release the round's held pulls
+  void FinishReducePush(const KVMeta& req, Group* g, KVServer<float>* server,
+                        hipStream_t stream);
   void HandlePull(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void RespondPull(const KVMeta& req, Group* g, KVServer<float>* server);
   Group* GroupFor(const SArray<Key>& keys);  // find-or-create round group

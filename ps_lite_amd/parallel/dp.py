@@ -21,7 +21,12 @@ import numpy as np
 
 class PSGradSync:
     def __init__(self, ps, worker, params, num_workers, device=-1,
-                 partition_bytes=4 << 20, mode=None, key_base=1 << 20):
+                 partition_bytes=4 << 20, mode=None, key_base=1 << 20, compress=None):
+        if compress not in (None, "mxfp8"):
+            raise ValueError(f"unknown compress={compress!r} (None or 'mxfp8')")
+        if compress and (device < 0 or (mode or "reduce") != "reduce"):
+            raise ValueError("compress='mxfp8' needs a GPU (device >= 0) and reduce mode")
+        self.compress = compress
         self.ps = ps
         self.worker = worker
         self.params = list(params)
@@ -48,7 +53,13 @@ class PSGradSync:
         # straight from grad memory — no staging buffers, no copies
         self.direct = None
         for _, _, elems in self.buckets:
-            if device >= 0:
+            if compress:
+                # packed push and pull buffers (servers: dtype="mxfp8");
+                # grads are quantized from and dequantized into .grad
+                nbytes = ps._core.mxfp8_packed_nbytes(elems)
+                self.bufs.append(ps.pool_alloc(nbytes))
+                self.pull_bufs.append(ps.pool_alloc(nbytes))
+            elif device >= 0:
                 self.bufs.append(ps.pool_alloc(elems * 4))
                 self.pull_bufs.append(ps.pool_alloc(elems * 4))
             else:
@@ -69,10 +80,39 @@ class PSGradSync:
         pi, off, elems = self.buckets[b]
         return self.params[pi].grad.detach().reshape(-1)[off:off + elems]
 
+    def _allreduce_mxfp8(self):
+        """The reduce round on MXFP8 payloads (528 bytes per 512 elements
+        each way): quantize from .grad, push and pull packed bytes,
+        dequantize into .grad with the 1/num_workers scale folded in.
+        The servers run set_gpu_dense_handle(mode="reduce", dtype="mxfp8")."""
+        core = self.ps._core
+        keys = self._keys()
+        tss = []
+        for b, k in enumerate(keys):
+            elems = self.buckets[b][2]
+            nbytes = core.mxfp8_packed_nbytes(elems)
+            core.k_mx_quantize(self._grad_view(b).data_ptr(), elems, self.bufs[b].ptr)
+            ka = np.array([k], dtype=np.uint64)
+            lens = np.array([nbytes // 4], dtype=np.int32)
+            tss.append(self.worker.zpush_ptr(ka, self.bufs[b].ptr, nbytes, self.device, lens,
+                                             cmd=2))
+            tss.append(self.worker.zpull_ptr(ka, self.pull_bufs[b].ptr, nbytes, self.device,
+                                             lens))
+        for ts in tss:
+            self.worker.wait(ts)
+        inv = 1.0 / self.num_workers
+        for b in range(len(self.buckets)):
+            elems = self.buckets[b][2]
+            core.k_mx_dequantize(self.pull_bufs[b].ptr, elems, self._grad_view(b).data_ptr(), inv)
+        self.step_count += 1
+
     def allreduce(self):
         """Average .grad across workers, in place. Call after backward."""
         import torch
 
+        if self.compress:
+            self._allreduce_mxfp8()
+            return
         if self.direct is None:
             # direct (zero-staging) mode needs every grad bucket inside
             # the zero-copy pool window AND reduce-mode servers (pulls
