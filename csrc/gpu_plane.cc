@@ -9,6 +9,7 @@
 
 #include <cstring>
 
+#include "hip_check.h"
 #include "hip_pool.h"
 #include "host_par.h"
 #include "host_pool.h"
@@ -19,12 +20,6 @@
 namespace xps {
 
 static const size_t kInlineMax = 4096;  // host blobs above this ride the shm pool
-
-#define XPS_HIP_CHECK(cmd)                                                            \
-  do {                                                                                \
-    hipError_t e_ = (cmd);                                                            \
-    XPS_CHECK(e_ == hipSuccess) << "HIP error: " << hipGetErrorString(e_) << " in " #cmd; \
-  } while (0)
 
 // count of blobs received BY REFERENCE (pool offset, no copy) — the
 // zero-copy assertion hook (reference test_benchmark.cc:169-181 checks

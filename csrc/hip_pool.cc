@@ -1,16 +1,9 @@
 #include "hip_pool.h"
 
-#include <hip/hip_runtime.h>
-
 #include "base.h"
+#include "hip_check.h"
 
 namespace xps {
-
-#define XPS_HIP_CHECK(cmd)                                                            \
-  do {                                                                                \
-    hipError_t e_ = (cmd);                                                            \
-    XPS_CHECK(e_ == hipSuccess) << "HIP error: " << hipGetErrorString(e_) << " in " #cmd; \
-  } while (0)
 
 static const size_t kAlign = 512;
 

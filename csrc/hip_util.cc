@@ -1,15 +1,9 @@
 #include "hip_util.h"
 
-#include <hip/hip_runtime.h>
+#include "hip_check.h"
 
 namespace xps {
 namespace gpu {
-
-#define XPS_HIP_CHECK(cmd)                                                            \
-  do {                                                                                \
-    hipError_t e_ = (cmd);                                                            \
-    XPS_CHECK(e_ == hipSuccess) << "HIP error: " << hipGetErrorString(e_) << " in " #cmd; \
-  } while (0)
 
 int DeviceCount() {
   static int count = []() {

@@ -1,6 +1,7 @@
 #include "server_handlers.h"
 
 #include "gpu_plane.h"
+#include "hip_check.h"
 #include "hip_pool.h"
 #include "kernels.h"
 #include "mxfp8.h"
@@ -9,30 +10,17 @@ namespace xps {
 
 std::atomic<uint64_t> g_mx_launches{0};
 
-#define XPS_HIP_CHECK(cmd)                                                            \
-  do {                                                                                \
-    hipError_t e_ = (cmd);                                                            \
-    XPS_CHECK(e_ == hipSuccess) << "HIP error: " << hipGetErrorString(e_) << " in " #cmd; \
-  } while (0)
-
 static GpuPlane* ThePlane(Postoffice* po) {
   return dynamic_cast<GpuPlane*>(po->van() ? po->van()->plane() : nullptr);
 }
 
-static hipStream_t PeerStream(Postoffice* po, int sender, hipStream_t* fallback) {
-  auto* plane = ThePlane(po);
-  if (plane) return plane->StreamForPeer(sender);
-  if (!*fallback) {
-    XPS_HIP_CHECK(hipStreamCreateWithFlags(fallback, hipStreamNonBlocking));
+// The peer's lane 0 (push kernels) or its pull-response lane: copies there
+// overlap the next push kernel on lane 0; same-key ordering rides the
+// handler's event chain. Without a plane one fallback stream serves both.
+static hipStream_t LaneStream(Postoffice* po, int sender, bool pull, hipStream_t* fallback) {
+  if (auto* plane = ThePlane(po)) {
+    return pull ? plane->PullStreamForPeer(sender) : plane->StreamForPeer(sender);
   }
-  return *fallback;
-}
-
-// pull-response lane: copies here overlap the next push kernel on the
-// peer's lane 0; same-key ordering rides the handler's event chain
-static hipStream_t PeerPullStream(Postoffice* po, int sender, hipStream_t* fallback) {
-  auto* plane = ThePlane(po);
-  if (plane) return plane->PullStreamForPeer(sender);
   if (!*fallback) {
     XPS_HIP_CHECK(hipStreamCreateWithFlags(fallback, hipStreamNonBlocking));
   }
@@ -56,12 +44,61 @@ static void EventFree(Postoffice* po, hipEvent_t ev) {
 
 // ------------------------------------------------------------------ dense
 
-// Does the van stage this pull response's device vals through host memory
-// (no in-place HBM destination: none advertised, or a host-pool one)? Its
-// device-to-host copy is stream-unaware, so the handler drains its stream
-// first.
-static bool StagedOnHost(int option) {
-  return !(option & kOptPullAddr) || (option & kOptHostAddr);
+// Did the requester advertise an in-place HBM destination (kOptHostAddr
+// names an offset in the host pool instead)? Without one the van stages the
+// response's device vals through host memory; its device-to-host copy is
+// stream-unaware, so the handler drains its stream first.
+static bool HbmDest(int option) {
+  return (option & kOptPullAddr) && !(option & kOptHostAddr);
+}
+
+// byte length of key i of n: lens omitted = equal split of vals
+static inline size_t LenOf(const KVPairs<float>& kvs, size_t i, size_t n) {
+  return kvs.lens.empty() ? kvs.vals.nbytes() / n
+                          : static_cast<size_t>(kvs.lens[i]) * sizeof(float);
+}
+
+// descs hold dst and nbytes: segment i reads vals where segment i-1 ended
+static void SliceInto(std::vector<kern::CopyDesc>* descs, const void* vals) {
+  size_t off = 0;
+  for (auto& d : *descs) {
+    d.src = static_cast<const char*>(vals) + off;
+    off += d.nbytes;
+  }
+}
+
+// one batched kernel for the list, or one launch per segment when a pointer
+// or length is off the 16 B grid
+static void CopySegments(const std::vector<kern::CopyDesc>& descs, hipStream_t s) {
+  if (kern::BatchAligned(descs.data(), descs.size())) {
+    kern::BatchedAssign(descs.data(), static_cast<int>(descs.size()), s);
+  } else {
+    for (auto& d : descs) kern::DenseAssign(d.dst, d.src, d.nbytes, s);
+  }
+}
+
+// descs hold src and nbytes: pack them back to back into a fresh pool buffer
+// (the plane keeps it alive until the response is sent)
+static SArray<float> PackStaged(std::vector<kern::CopyDesc>* descs, hipStream_t s) {
+  size_t total = 0;
+  for (auto& d : *descs) total += d.nbytes;
+  SArray<char> tmp = HbmPool::Get()->AllocArray(total);
+  size_t off = 0;
+  for (auto& d : *descs) {
+    d.dst = tmp.data() + off;
+    off += d.nbytes;
+  }
+  CopySegments(*descs, s);
+  return SArray<float>::View(tmp);
+}
+
+// Answer a pull with vals that the plane writes in place on `stream`, or
+// that the van stages through the host (TCP fallback)
+static void RespondStaged(KVMeta r, const KVPairs<float>& res, hipStream_t stream,
+                          KVServer<float>* server) {
+  if (!HbmDest(r.option)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+  r.option |= kOptPullLane;  // ordering prepared on the pull lane
+  server->Response(r, res);  // plane enqueues the in-place read on `stream`
 }
 
 static EventRef MakeEventRef(Postoffice* po, hipStream_t s) {
@@ -99,6 +136,14 @@ void GpuDenseHandler::BatchedSum(const kern::CopyDesc* descs, int n, hipStream_t
   }
 }
 
+void GpuDenseHandler::SumSegments(const std::vector<kern::CopyDesc>& descs, hipStream_t s) {
+  if (kern::BatchAligned(descs.data(), descs.size())) {
+    BatchedSum(descs.data(), static_cast<int>(descs.size()), s);
+  } else {
+    for (auto& d : descs) SumKernel(d.dst, d.src, d.nbytes, s);
+  }
+}
+
 bool GpuDenseHandler::NeedChain(int sender) {
   if (chain_) return true;
   // lane split for this peer (cross-device): push kernels on lane 0 and
@@ -113,7 +158,9 @@ void GpuDenseHandler::OrderAfter(Entry* e, hipStream_t s) {
   if (e->last_ev) XPS_HIP_CHECK(hipStreamWaitEvent(s, e->last_ev.get(), 0));
 }
 
-void GpuDenseHandler::Replace(Entry* e, size_t len) {
+GpuDenseHandler::Entry* GpuDenseHandler::EntryLocked(Key key, size_t len) {
+  Entry* e = &store_[key];
+  if (e->buf.size() >= len) return e;
   // retire (never free) a smaller buffer: workers may hold its offset in
   // their one-sided entry caches — a stale write must land in
   // dead-but-owned memory, not a reused pool region
@@ -122,14 +169,26 @@ void GpuDenseHandler::Replace(Entry* e, size_t len) {
   // zero before publishing: another peer's stream may accumulate into
   // this entry concurrently with our first push
   XPS_HIP_CHECK(hipMemset(e->buf.data(), 0, len));
+  return e;
+}
+
+GpuDenseHandler::Entry* GpuDenseHandler::EntryFor(Key key, size_t len) {
+  std::lock_guard<std::mutex> lk(mu_);
+  return EntryLocked(key, len);
+}
+
+void GpuDenseHandler::GrowReduce(Entry* e, size_t len) {
+  // no retire and no zeroing, unlike EntryLocked: a round's first push
+  // overwrites, and a hipMemset is a blocking call on the hot path
+  if (e->buf.size() < len) e->buf = HbmPool::Get()->AllocArray(len);
 }
 
 hipStream_t GpuDenseHandler::Stream(int sender) {
-  return PeerStream(po_, sender, &fallback_stream_);
+  return LaneStream(po_, sender, /*pull=*/false, &fallback_stream_);
 }
 
 hipStream_t GpuDenseHandler::PullStream(int sender) {
-  return PeerPullStream(po_, sender, &fallback_stream_);
+  return LaneStream(po_, sender, /*pull=*/true, &fallback_stream_);
 }
 
 void GpuDenseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
@@ -171,9 +230,8 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
   if (!FusedAssignEnabled()) return false;
   if (mode_ != DenseMode::kAssign || req.cmd == kCmdSum) return false;
   if (kvs.keys.size() != 1 || !kvs.vals.on_device()) return false;
-  if (!(req.option & kOptPullAddr) || (req.option & kOptHostAddr)) return false;
-  size_t len = kvs.lens.empty() ? kvs.vals.nbytes()
-                                : static_cast<size_t>(kvs.lens[0]) * sizeof(float);
+  if (!HbmDest(req.option)) return false;
+  size_t len = LenOf(kvs, 0, 1);
   if (len == 0 || len != kvs.vals.nbytes() || static_cast<int64_t>(len) != req.val_len) {
     return false;
   }
@@ -183,13 +241,7 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
   if (!dst) return false;
   XPS_STAGE(dense_fused_assign);
   XPS_HIP_CHECK(hipSetDevice(HbmPool::Get()->device()));
-  Entry* e;
-  {
-    // allocate / retire / zero / grow exactly as HandlePush does
-    std::lock_guard<std::mutex> lk(mu_);
-    e = &store_[kvs.keys[0]];
-    if (e->buf.size() < len) Replace(e, len);
-  }
+  Entry* e = EntryFor(kvs.keys[0], len);
   // a LARGER entry keeps its tail: the pull would return more than was
   // pushed — that is the two-step path's business
   if (e->buf.size() != len) return false;
@@ -213,7 +265,8 @@ bool GpuDenseHandler::TryFusedAssign(const KVMeta& req, const KVPairs<float>& kv
   g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
   // meta-only in-place response; the work ran on the PUSH lane, so no
   // kOptPullLane — the plane defers delivery on that lane's event. The
-  // entry advert rides along so the worker can go one-sided next time.
+  // entry advert rides along so the worker can go one-sided next time (in
+  // entry_addr: addr and val_len still describe the pull).
   KVMeta r = req;
   r.option |= kOptInPlace;
   r.option &= ~(kOptPullLane | kOptEntryPush);
@@ -269,10 +322,7 @@ void GpuDenseHandler::HandleReducePush(const KVMeta& req, const KVPairs<float>& 
   XPS_CHECK(kvs.vals.on_device()) << "reduce mode needs device vals (pool buffers)";
   if (g->lens.size() != n) {
     g->lens.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-      g->lens[i] = kvs.lens.empty() ? kvs.vals.nbytes() / n
-                                    : static_cast<size_t>(kvs.lens[i]) * sizeof(float);
-    }
+    for (size_t i = 0; i < n; ++i) g->lens[i] = LenOf(kvs, i, n);
   }
   hipStream_t stream = Stream(req.sender);
   XPS_HIP_CHECK(hipSetDevice(HbmPool::Get()->device()));
@@ -294,28 +344,15 @@ void GpuDenseHandler::HandleReducePush(const KVMeta& req, const KVPairs<float>& 
   // rn50 buckets at kMaxBatch=64), one event per push
   std::vector<kern::CopyDesc> descs;
   descs.reserve(n);
-  size_t off = 0;
   for (size_t i = 0; i < n; ++i) {
-    size_t len = g->lens[i];
-    Entry* e = g->ents[i];
-    if (e->buf.size() < len) e->buf = HbmPool::Get()->AllocArray(len);
-    descs.push_back({e->buf.data(), reinterpret_cast<const char*>(kvs.vals.data()) + off, len});
-    off += len;
+    GrowReduce(g->ents[i], g->lens[i]);
+    descs.push_back({g->ents[i]->buf.data(), nullptr, g->lens[i]});
   }
-  if (kern::BatchAligned(descs.data(), n)) {
-    if (first) {
-      kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
-    } else {
-      BatchedSum(descs.data(), static_cast<int>(n), stream);
-    }
+  SliceInto(&descs, kvs.vals.data());
+  if (first) {
+    CopySegments(descs, stream);
   } else {
-    for (auto& d : descs) {
-      if (first) {
-        kern::DenseAssign(d.dst, d.src, d.nbytes, stream);
-      } else {
-        SumKernel(d.dst, d.src, d.nbytes, stream);
-      }
-    }
+    SumSegments(descs, stream);
   }
   FinishReducePush(req, g, server, stream);
 }
@@ -341,7 +378,7 @@ void GpuDenseHandler::ReducePushMx(Group* g, const KVPairs<float>& kvs, hipStrea
         << "mxfp8 push: key " << g->keys[i] << " has " << len
         << " payload bytes, not a multiple of the 528-byte superblock";
     Entry* e = g->ents[i];
-    if (e->buf.size() < len) e->buf = HbmPool::Get()->AllocArray(len);
+    GrowReduce(e, len);
     XPS_CHECK((reinterpret_cast<uintptr_t>(e->buf.data()) & 15u) == 0)
         << "mxfp8 push: the entry of key " << g->keys[i] << " is not 16 B-aligned";
     size_t acc_len = len / mx::kSuperBytes * mx::kSuperF32Bytes;
@@ -390,27 +427,21 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
   XPS_HIP_CHECK(hipSetDevice(HbmPool::Get()->device()));
   bool chain = NeedChain(req.sender);
   bool sum_all = mode_ == DenseMode::kAssign ? req.cmd == kCmdSum : req.cmd != kCmdAssign;
-  // multi-key device push: one batched kernel launch for all segments
+  // multi-key device push: one batched kernel launch for all segments. A
+  // list off the 16 B grid falls through to the per-key loop, not to
+  // per-segment launches: when chaining, that loop orders and publishes an
+  // event per key.
   if (kvs.vals.on_device() && n > 1) {
     std::vector<kern::CopyDesc> descs;
     std::vector<Entry*> ents;
     descs.reserve(n);
     ents.reserve(n);
-    size_t boff = 0;
     for (size_t i = 0; i < n; ++i) {
-      size_t len = kvs.lens.empty() ? kvs.vals.nbytes() / n
-                                    : static_cast<size_t>(kvs.lens[i]) * sizeof(float);
-      Entry* e;
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        e = &store_[kvs.keys[i]];
-        if (e->buf.size() < len) Replace(e, len);
-      }
-      ents.push_back(e);
-      descs.push_back({e->buf.data(),
-                       reinterpret_cast<const char*>(kvs.vals.data()) + boff, len});
-      boff += len;
+      size_t len = LenOf(kvs, i, n);
+      ents.push_back(EntryFor(kvs.keys[i], len));
+      descs.push_back({ents[i]->buf.data(), nullptr, len});
     }
+    SliceInto(&descs, kvs.vals.data());
     if (kern::BatchAligned(descs.data(), n)) {
       for (Entry* e : ents) OrderAfter(e, stream);
       if (sum_all) {
@@ -422,8 +453,7 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
         EventRef ev = MakeEventRef(po_, stream);  // one event covers the batch
         for (Entry* e : ents) e->last_ev = ev;
       }
-      auto* plane0 = po_->van() ? po_->van()->plane() : nullptr;
-      if (!plane0) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+      if (!ThePlane(po_)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
       if (respond) server->Response(req);
       return;
     }
@@ -432,22 +462,14 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
   bool synced = false;
   Entry* last_e = nullptr;
   for (size_t i = 0; i < n; ++i) {
-    size_t len = kvs.lens.empty() ? kvs.vals.nbytes() / n
-                                  : static_cast<size_t>(kvs.lens[i]) * sizeof(float);
-    Entry* e;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      e = &store_[kvs.keys[i]];
-      if (e->buf.size() < len) Replace(e, len);
-    }
-    last_e = e;
-    bool sum = sum_all;
+    size_t len = LenOf(kvs, i, n);
+    Entry* e = last_e = EntryFor(kvs.keys[i], len);
     const char* src = reinterpret_cast<const char*>(kvs.vals.data()) + off;
     if (kvs.vals.on_device()) {
       OrderAfter(e, stream);
       {
         XPS_STAGE(push_kernel_launch);
-        if (sum) {
+        if (sum_all) {
           SumKernel(e->buf.data(), src, len, stream);
         } else {
           kern::DenseAssign(e->buf.data(), src, len, stream);
@@ -465,7 +487,7 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
         e->last_ev.reset();
       }
       // host vals (TCP-staged path): correctness-first synchronous route
-      if (sum) {
+      if (sum_all) {
         SArray<char> scratch = HbmPool::Get()->AllocArray(len);
         XPS_HIP_CHECK(hipMemcpy(scratch.data(), src, len, hipMemcpyHostToDevice));
         SumKernel(e->buf.data(), scratch.data(), len, stream);
@@ -477,11 +499,13 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
     }
     off += len;
   }
-  auto* plane = po_->van() ? po_->van()->plane() : nullptr;
+  auto* plane = ThePlane(po_);
   if (!plane && !synced) XPS_HIP_CHECK(hipStreamSynchronize(stream));
   if (!respond) return;
   // assign mode, single key: advertise the store entry's pool offset so
-  // this worker's next pushes of the key go one-sided (kOptEntryPush)
+  // this worker's next pushes of the key go one-sided (kOptEntryPush). This
+  // advert names the entry in addr and val_len; the fused path's rides in
+  // entry_addr beside the pull's own addr.
   if (mode_ == DenseMode::kAssign && n == 1 && last_e && plane) {
     uint64_t eoff = 0;
     if (HbmPool::Get()->OffsetOf(last_e->buf.data(), &eoff)) {
@@ -496,6 +520,32 @@ void GpuDenseHandler::HandlePush(const KVMeta& req, const KVPairs<float>& kvs,
   server->Response(req);
 }
 
+// Pull written straight into the requester's advertised HBM pool range: one
+// batched copy of every segment (descs hold src and nbytes) and a meta-only
+// response that the plane defers on `stream`. False, with nothing launched or
+// sent, when there is no such destination, a segment does not resolve in the
+// peer's pool, or the list is off the 16 B grid. That the destination holds
+// every segment is the caller's to know.
+bool GpuDenseHandler::TryPullInPlace(const KVMeta& req, const KVPairs<float>& res,
+                                     std::vector<kern::CopyDesc>* descs, hipStream_t stream,
+                                     KVServer<float>* server) {
+  auto* plane = ThePlane(po_);
+  if (!plane || !HbmDest(req.option)) return false;
+  uint64_t off = 0;
+  for (auto& d : *descs) {
+    d.dst = plane->PeerDst(req.sender, req.addr + off, d.nbytes);
+    if (!d.dst) return false;
+    off += d.nbytes;
+  }
+  if (!kern::BatchAligned(descs->data(), descs->size())) return false;
+  kern::BatchedAssign(descs->data(), static_cast<int>(descs->size()), stream);
+  KVMeta r = req;
+  r.option |= kOptInPlace | kOptPullLane;
+  r.val_len = static_cast<int64_t>(off);
+  server->Response(r, res);  // keys and lens only
+  return true;
+}
+
 void GpuDenseHandler::RespondPull(const KVMeta& req, Group* g, KVServer<float>* server) {
   XPS_STAGE(reduce_respond_pull);
   hipStream_t stream = PullStream(req.sender);
@@ -503,71 +553,21 @@ void GpuDenseHandler::RespondPull(const KVMeta& req, Group* g, KVServer<float>* 
     XPS_HIP_CHECK(hipStreamWaitEvent(stream, ev.get(), 0));
   }
   size_t n = g->keys.size();
-  size_t total = 0;
-  for (size_t len : g->lens) total += len;
-  SArray<Key> keys(g->keys);
+  KVPairs<float> res;
+  res.keys = SArray<Key>(g->keys);
   SArray<int> lens(n);
-  for (size_t i = 0; i < n; ++i) lens[i] = static_cast<int>(g->lens[i] / sizeof(float));
-  bool responded = false;
-  // fast path: write the whole group straight into the requester's
-  // advertised HBM pool destination (one batched kernel, meta-only
-  // response); kOptHostAddr names an offset in the host pool instead
-  if ((req.option & kOptPullAddr) && !(req.option & kOptHostAddr)) {
-    if (auto* plane = ThePlane(po_)) {
-      std::vector<kern::CopyDesc> descs;
-      descs.reserve(n);
-      uint64_t off = 0;
-      bool ok = true;
-      for (size_t i = 0; i < n && ok; ++i) {
-        size_t len = g->lens[i];
-        char* dst = plane->PeerDst(req.sender, req.addr + off, len);
-        ok = dst != nullptr;
-        if (ok) {
-          descs.push_back({dst, g->ents[i]->buf.data(), len});
-          off += len;
-        }
-      }
-      ok = ok && kern::BatchAligned(descs.data(), descs.size());
-      if (ok) {
-        kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
-        KVMeta r2 = req;
-        r2.option |= kOptInPlace | kOptPullLane;
-        r2.val_len = static_cast<int64_t>(total);
-        KVPairs<float> res2;
-        res2.keys = keys;
-        res2.lens = lens;
-        server->Response(r2, res2);  // plane defers the meta on `stream`
-        responded = true;
-      }
-    }
+  std::vector<kern::CopyDesc> descs;
+  descs.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    lens[i] = static_cast<int>(g->lens[i] / sizeof(float));
+    descs.push_back({nullptr, g->ents[i]->buf.data(), g->lens[i]});
   }
-  if (!responded) {
-    // staging path (TCP fallback / no advertised destination)
-    KVPairs<float> res;
-    res.keys = keys;
-    res.lens = lens;
-    if (n == 1) {
-      res.vals = SArray<float>::View(g->ents[0]->buf);
-    } else {
-      SArray<char> tmp = HbmPool::Get()->AllocArray(total);
-      std::vector<kern::CopyDesc> descs;
-      descs.reserve(n);
-      size_t off = 0;
-      for (size_t i = 0; i < n; ++i) {
-        descs.push_back({tmp.data() + off, g->ents[i]->buf.data(), g->lens[i]});
-        off += g->lens[i];
-      }
-      if (kern::BatchAligned(descs.data(), n)) {
-        kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
-      } else {
-        for (auto& d : descs) kern::DenseAssign(d.dst, d.src, d.nbytes, stream);
-      }
-      res.vals = SArray<float>::View(tmp);  // plane keeps it alive until sent
-    }
-    if (StagedOnHost(req.option)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
-    KVMeta r = req;
-    r.option |= kOptPullLane;  // ordering prepared on the pull lane
-    server->Response(r, res);  // plane enqueues the in-place read on `stream`
+  res.lens = lens;
+  // req.val_len does not bound the in-place write here; in HandlePull it does
+  if (!TryPullInPlace(req, res, &descs, stream, server)) {
+    // staging path (TCP fallback / no advertised destination / off the 16 B grid)
+    res.vals = n == 1 ? SArray<float>::View(g->ents[0]->buf) : PackStaged(&descs, stream);
+    RespondStaged(req, res, stream, server);
   }
   EventRef pe = MakeEventRef(po_, stream);
   g->pull_guard.push_back(pe);
@@ -622,121 +622,52 @@ void GpuDenseHandler::HandlePull(const KVMeta& req, const KVPairs<float>& kvs,
   }
   hipStream_t stream = PullStream(req.sender);
   bool chain = NeedChain(req.sender);
-  // multi-key pull with an in-place destination: batched copy of every
-  // store entry straight into the requester's mapped pool (no staging
-  // buffer, meta-only response). The destination is an HBM one
-  // (kOptHostAddr names an offset in the host pool) and holds every entry:
-  // entries that grew since the worker sized its buffer go through the
-  // staging branch below, which strips kOptPullAddr for them.
-  if (n > 1 && (req.option & kOptPullAddr) && !(req.option & kOptHostAddr)) {
-    if (auto* plane = ThePlane(po_)) {
-      std::vector<kern::CopyDesc> descs;
-      std::vector<Entry*> ents;
-      SArray<int> lens2(n);
-      uint64_t off = 0;
-      bool ok = true;
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        for (size_t i = 0; i < n && ok; ++i) {
-          auto it = store_.find(kvs.keys[i]);
-          XPS_CHECK(it != store_.end()) << "pull of unknown key " << kvs.keys[i];
-          size_t len = it->second.buf.size();
-          char* dst = plane->PeerDst(req.sender, req.addr + off, len);
-          ok = dst != nullptr;
-          if (ok) {
-            ents.push_back(&it->second);
-            descs.push_back({dst, it->second.buf.data(), len});
-            lens2[i] = static_cast<int>(len / sizeof(float));
-            off += len;
-          }
-        }
-      }
-      ok = ok && kern::BatchAligned(descs.data(), descs.size()) &&
-           !(req.val_len > 0 && off > static_cast<uint64_t>(req.val_len));
-      if (ok) {
-        for (Entry* e : ents) OrderAfter(e, stream);
-        kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
-        KVMeta r2 = req;
-        r2.option |= kOptInPlace | kOptPullLane;
-        r2.val_len = static_cast<int64_t>(off);
-        KVPairs<float> res2;
-        res2.keys = kvs.keys;
-        res2.lens = lens2;
-        server->Response(r2, res2);  // meta+keys/lens only; plane defers on `stream`
-        if (chain) {
-          EventRef ev = MakeEventRef(po_, stream);  // pushes must wait these reads
-          for (Entry* e : ents) e->last_ev = ev;
-        }
-        return;
-      }
-    }
-  }
   KVPairs<float> res;
   res.keys = kvs.keys;
   SArray<int> lens(n);
   std::vector<Entry*> touched;
-  if (n == 1) {
-    SArray<char> entry;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      auto it = store_.find(kvs.keys[0]);
-      XPS_CHECK(it != store_.end()) << "pull of unknown key " << kvs.keys[0];
-      entry = it->second.buf;
+  SArray<char> entry;                  // n == 1: served as a zero-copy store view
+  std::vector<kern::CopyDesc> descs;  // n > 1: whole entries, in key order
+  if (n > 1) descs.reserve(n);
+  size_t total = 0;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    for (size_t i = 0; i < n; ++i) {
+      auto it = store_.find(kvs.keys[i]);
+      XPS_CHECK(it != store_.end()) << "pull of unknown key " << kvs.keys[i];
+      const SArray<char>& buf = it->second.buf;
       touched.push_back(&it->second);
-    }
-    // the plane's in-place write (or the sync below) reads buf on
-    // `stream`: order it behind the last writer
-    {
-      XPS_STAGE(pull_order_after);
-      OrderAfter(touched[0], stream);
-    }
-    res.vals = SArray<float>::View(entry);  // zero-copy store view
-    lens[0] = static_cast<int>(entry.size() / sizeof(float));
-  } else {
-    size_t total = 0;
-    std::vector<SArray<char>> entries(n);
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      for (size_t i = 0; i < n; ++i) {
-        auto it = store_.find(kvs.keys[i]);
-        XPS_CHECK(it != store_.end()) << "pull of unknown key " << kvs.keys[i];
-        entries[i] = it->second.buf;
-        touched.push_back(&it->second);
-        lens[i] = static_cast<int>(entries[i].size() / sizeof(float));
-        total += entries[i].size();
+      lens[i] = static_cast<int>(buf.size() / sizeof(float));
+      total += buf.size();
+      if (n == 1) {
+        entry = buf;
+      } else {
+        descs.push_back({nullptr, buf.data(), buf.size()});
       }
     }
-    for (Entry* e : touched) OrderAfter(e, stream);
-    SArray<char> tmp = HbmPool::Get()->AllocArray(total);
-    size_t off = 0;
-    std::vector<kern::CopyDesc> descs;
-    descs.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-      descs.push_back({tmp.data() + off, entries[i].data(), entries[i].size()});
-      off += entries[i].size();
-    }
-    if (kern::BatchAligned(descs.data(), n)) {
-      kern::BatchedAssign(descs.data(), static_cast<int>(n), stream);
-    } else {
-      for (auto& d : descs) kern::DenseAssign(d.dst, d.src, d.nbytes, stream);
-    }
-    res.vals = SArray<float>::View(tmp);  // plane keeps it alive until sent
   }
   res.lens = lens;
-  KVMeta r = req;
-  // the advertised destination can be SMALLER than the store entry
-  // (entry grew since the worker sized its buffer): an in-place write
-  // would overrun the requester's pool region — force the staging path,
-  // whose worker-side merge checks the overflow loudly
-  if ((r.option & kOptPullAddr) &&
-      static_cast<int64_t>(res.vals.nbytes()) > req.val_len && req.val_len > 0) {
-    r.option &= ~kOptPullAddr;
+  // the copies below (ours, the plane's in-place write, or the sync) read
+  // the entries on `stream`: order it behind their last writers
+  {
+    XPS_STAGE(pull_order_after);
+    for (Entry* e : touched) OrderAfter(e, stream);
   }
-  // TCP fallback (no in-place HBM destination): the staging D2H copy below
-  // in the van is stream-unaware — drain our stream first
-  if (StagedOnHost(r.option)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
-  r.option |= kOptPullLane;  // ordering prepared on the pull lane
-  server->Response(r, res);  // plane enqueues the in-place read on `stream`
+  // the advertised destination can be SMALLER than the store entries (an
+  // entry grew since the worker sized its buffer): an in-place write would
+  // overrun the requester's pool region
+  bool fits = !(req.val_len > 0 && static_cast<int64_t>(total) > req.val_len);
+  // several keys go straight into the requester's mapped pool when they fit
+  // (no staging buffer); one key is the plane's in-place write of the view
+  if (!(n > 1 && fits && TryPullInPlace(req, res, &descs, stream, server))) {
+    res.vals = n == 1 ? SArray<float>::View(entry) : PackStaged(&descs, stream);
+    KVMeta r = req;
+    // too small a destination: force the staging path, whose worker-side
+    // merge checks the overflow loudly
+    if (!fits) r.option &= ~kOptPullAddr;
+    RespondStaged(r, res, stream, server);
+  }
+  // after the response in either branch
   if (chain) {
     EventRef ev = MakeEventRef(po_, stream);  // pushes must wait these reads
     for (Entry* e : touched) e->last_ev = ev;
@@ -783,9 +714,8 @@ void GpuDenseHandler::Load(const std::string& path) {
     XPS_CHECK_EQ(fread(&len, 8, 1, f), 1u);
     host.resize(len);
     XPS_CHECK_EQ(fread(host.data(), 1, len, f), len);
-    auto& e = store_[key];
-    if (e.buf.size() < len) Replace(&e, len);
-    XPS_HIP_CHECK(hipMemcpy(e.buf.data(), host.data(), len, hipMemcpyHostToDevice));
+    Entry* e = EntryLocked(key, len);
+    XPS_HIP_CHECK(hipMemcpy(e->buf.data(), host.data(), len, hipMemcpyHostToDevice));
   }
   fclose(f);
 }
@@ -816,7 +746,7 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
 }
 
 hipStream_t GpuSparseHandler::Stream(int sender) {
-  return PeerStream(po_, sender, &fallback_stream_);
+  return LaneStream(po_, sender, /*pull=*/false, &fallback_stream_);
 }
 
 const uint64_t* GpuSparseHandler::DeviceKeys(const SArray<Key>& keys, int sender,
@@ -837,10 +767,27 @@ const uint64_t* GpuSparseHandler::DeviceKeys(const SArray<Key>& keys, int sender
   return reinterpret_cast<const uint64_t*>(scratch.data());
 }
 
+// gather the n rows on `stream` and answer the pull with them
+void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n,
+                                     hipStream_t stream, KVServer<float>* server) {
+  SArray<char> out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
+  kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
+                        reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_, rows_);
+  KVPairs<float> res;
+  // keys stay meta-only: device keys must not be dereferenced host-side
+  res.vals = SArray<float>::View(out);
+  SArray<int> lens(1);
+  lens[0] = static_cast<int>(n * row_len_);
+  res.lens = lens;
+  // drained whenever no destination was advertised; the dense handlers'
+  // HbmDest also drains for a host-pool destination
+  if (!(req.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+  server->Response(req, res);
+}
+
 void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
                                   KVServer<float>* server) {
-  auto* pool = HbmPool::Get();
-  XPS_HIP_CHECK(hipSetDevice(pool->device()));
+  XPS_HIP_CHECK(hipSetDevice(HbmPool::Get()->device()));
   hipStream_t stream = Stream(req.sender);
   size_t n = kvs.keys.size();
   XPS_CHECK_GT(n, 0u);
@@ -859,40 +806,15 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
     if (req.pull) {
       // fused round (ZPushPull): gather the post-scatter rows on the
       // SAME stream (ordered behind the scatter) and answer in one trip
-      SArray<char> out = pool->AllocArray(n * row_len_ * sizeof(float));
-      kern::SparseGatherF32(table, rows, n, row_len_, reinterpret_cast<float*>(out.data()),
-                            stream, key_shift_, row_base_, rows_);
-      KVPairs<float> res;
-      res.vals = SArray<float>::View(out);
-      SArray<int> lens(1);
-      lens[0] = static_cast<int>(n * row_len_);
-      res.lens = lens;
-      if (!(req.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
-      server->Response(req, res);
+      GatherRespond(req, rows, n, stream, server);
       return;
     }
-    auto* plane = po_->van() ? po_->van()->plane() : nullptr;
-    if (!plane) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+    if (!ThePlane(po_)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
     server->Response(req);
   } else if (req.pull) {
-    const uint64_t* rows = DeviceKeys(kvs.keys, req.sender, stream);
-    SArray<char> out = pool->AllocArray(n * row_len_ * sizeof(float));
-    kern::SparseGatherF32(table, rows, n, row_len_, reinterpret_cast<float*>(out.data()), stream,
-                          key_shift_, row_base_, rows_);
-    KVPairs<float> res;
-    // keys stay meta-only: device keys must not be dereferenced host-side
-    res.vals = SArray<float>::View(out);
-    SArray<int> lens(1);
-    lens[0] = static_cast<int>(n * row_len_);
-    res.lens = lens;
-    if (!(req.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
-    server->Response(req, res);
+    GatherRespond(req, DeviceKeys(kvs.keys, req.sender, stream), n, stream, server);
   }
 }
-
-}  // namespace xps
-
-namespace xps {
 
 void GpuSparseHandler::Save(const std::string& path) {
   FILE* f = fopen(path.c_str(), "wb");

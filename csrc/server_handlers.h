@@ -127,6 +127,11 @@ class GpuDenseHandler {
                         hipStream_t stream);
   void HandlePull(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   void RespondPull(const KVMeta& req, Group* g, KVServer<float>* server);
+  // multi-key pull copied straight into the requester's advertised HBM
+  // destination, meta-only response; false = not possible, nothing done
+  bool TryPullInPlace(const KVMeta& req, const KVPairs<float>& res,
+                      std::vector<kern::CopyDesc>* descs, hipStream_t stream,
+                      KVServer<float>* server);
   Group* GroupFor(const SArray<Key>& keys);  // find-or-create round group
   hipStream_t Stream(int sender);      // lane 0: push/accumulate kernels
   hipStream_t PullStream(int sender);  // pull lane: response copies
@@ -134,13 +139,18 @@ class GpuDenseHandler {
   // peer's lanes actually split = cross-device)
   bool NeedChain(int sender);
   void OrderAfter(Entry* e, hipStream_t s);  // wait the entry's last_ev
-  // give a too-small entry a zeroed buffer of exactly len bytes; the old
-  // one is retired, never freed (mu_ held)
-  static void Replace(Entry* e, size_t len);
+  // find or create the key's entry; a too-small one gets a zeroed buffer
+  // of exactly len bytes and its old one is retired, never freed.
+  // EntryFor takes mu_, EntryLocked wants it held.
+  Entry* EntryFor(Key key, size_t len);
+  Entry* EntryLocked(Key key, size_t len);
+  static void GrowReduce(Entry* e, size_t len);  // reduce mode: plain reallocation
 
   // dtype-dispatched accumulate (nbytes, not elements)
   void SumKernel(void* dst, const void* src, size_t nbytes, hipStream_t s);
   void BatchedSum(const kern::CopyDesc* descs, int n, hipStream_t s);
+  // BatchedSum, or SumKernel per segment when the list is off the 16 B grid
+  void SumSegments(const std::vector<kern::CopyDesc>& descs, hipStream_t s);
 
   Postoffice* po_;
   DenseMode mode_;
@@ -175,6 +185,8 @@ class GpuSparseHandler {
   // keys usable by a kernel: device keys pass through; host keys are
   // staged synchronously into a per-peer scratch row-id buffer
   const uint64_t* DeviceKeys(const SArray<Key>& keys, int sender, hipStream_t s);
+  void GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n, hipStream_t stream,
+                     KVServer<float>* server);
 
   Postoffice* po_;
   size_t rows_;

@@ -595,6 +595,16 @@ def _reduce_f32_fn(ps_mod, rank):
     return _reduce_rounds(ps_mod, rank, "f32", [1024, 3, 4096, 64], seed=21)
 
 
+def _reduce_one_3_fn(ps_mod, rank):
+    # a group of one key, 12 bytes: the staging pull answers with a view of the entry
+    return _reduce_rounds(ps_mod, rank, "f32", [3], seed=25)
+
+
+def _reduce_one_1024_fn(ps_mod, rank):
+    # a group of one key, 16-byte multiple: the in-place batched pull of one segment
+    return _reduce_rounds(ps_mod, rank, "f32", [1024], seed=26)
+
+
 def _reduce_bf16_fn(ps_mod, rank):
     return _reduce_rounds(ps_mod, rank, "bf16", [1024, 64, 2048], seed=22)
 
@@ -607,7 +617,8 @@ def _two_procs(fn):
 
 @gpu
 def test_reduce_rounds_f32_two_procs():
-    _two_procs(_reduce_f32_fn)
+    for fn in (_reduce_f32_fn, _reduce_one_3_fn, _reduce_one_1024_fn):
+        _two_procs(fn)
 
 
 @gpu
