@@ -648,6 +648,76 @@ static bool NeedsStaging(const Message& msg) {
          (!(msg.meta.option & kOptPullAddr) || (msg.meta.option & kOptHostAddr));
 }
 
+// pull response whose requester advertised where the values go ...
+static bool HasPullDest(const Message& msg) {
+  return !msg.meta.request && msg.meta.pull && msg.data.size() > 1 &&
+         (msg.meta.option & kOptPullAddr);
+}
+// ... HOST vals for a destination in its host pool
+static bool HostDest(const Message& msg) {
+  return (msg.meta.option & kOptHostAddr) && !msg.data[1].on_device() && msg.data[1].size() > 0;
+}
+// ... device vals for a destination in its HBM pool
+static bool HbmDest(const Message& msg) {
+  return !(msg.meta.option & kOptHostAddr) && msg.data[1].on_device();
+}
+
+// The synchronous-handler contract: a host handler's response may be a
+// VIEW of mutable server state, and the store may mutate right after
+// Response returns. The wire paths serialize before that; a same-process
+// delivery takes a private copy instead.
+static SArray<char> Snapshot(const SArray<char>& d) {
+  SArray<char> copy(d.size());
+  memcpy(copy.data(), d.data(), d.size());
+  return copy;
+}
+
+// what an in-place note does with the host blobs it keeps
+enum class NoteBlobs {
+  kShare,       // same buffers as msg
+  kSnapshot,    // private copies (see Snapshot)
+  kInlineOnly,  // shared, minus blobs over kInlineMax: the note must fit the ring
+};
+
+// The meta-only message that follows an in-place write of msg's vals
+// (blob 1): msg's meta with kOptInPlace and val_len set, plus msg's host
+// blobs other than blob 1 (keys/lens for the merge bookkeeping), with
+// data_type rebuilt to match.
+static Message InPlaceNote(const Message& msg, size_t val_len,
+                           NoteBlobs how = NoteBlobs::kShare) {
+  Message note;
+  note.meta = msg.meta;
+  note.meta.option |= kOptInPlace;
+  note.meta.val_len = static_cast<int64_t>(val_len);
+  note.meta.data_type.clear();
+  for (size_t i = 0; i < msg.data.size(); ++i) {
+    const SArray<char>& d = msg.data[i];
+    if (i == 1 || d.on_device()) continue;
+    if (how == NoteBlobs::kInlineOnly && d.size() > kInlineMax) continue;
+    note.data.push_back(how == NoteBlobs::kSnapshot ? Snapshot(d) : d);
+    note.meta.data_type.push_back(msg.meta.data_type[i]);
+  }
+  return note;
+}
+
+// the vals of an in-place write stay alive until its event fires
+static Message KeepAlive(const SArray<char>& vals) {
+  Message keepalive;
+  keepalive.data.push_back(vals);
+  return keepalive;
+}
+
+static GpuPlane* PlaneOf(Postoffice* po) {
+  return dynamic_cast<GpuPlane*>(po->van() ? po->van()->plane() : nullptr);
+}
+
+// XPS_LOCAL_QUEUE_REQ=1: same-process requests are queued to the
+// receiver's poll thread instead of delivered inline
+static bool LocalQueueReq() {
+  static const bool on = Environment::Get()->GetInt("XPS_LOCAL_QUEUE_REQ", 0) != 0;
+  return on;
+}
+
 bool GpuPlane::CanSend(const Message& msg, const Node& peer) {
   if (!started_ || stop_.load()) return false;
   if (peer.host_hash != my_host_hash_ || peer.shm_uid == 0) return false;
@@ -734,8 +804,7 @@ void GpuPlane::DeliverLocal(Postoffice* lpo, Message& msg, int64_t bytes) {
   // customer.cc). Requests deliver inline by default (lowest latency —
   // measured better than queue-pipelining for single-flow traffic);
   // XPS_LOCAL_QUEUE_REQ=1 opts into the queued/pipelined variant.
-  static const bool queue_req = Environment::Get()->GetInt("XPS_LOCAL_QUEUE_REQ", 0) != 0;
-  if (InCustomerHandler() || (queue_req && msg.meta.request)) {
+  if (InCustomerHandler() || (LocalQueueReq() && msg.meta.request)) {
     if (rplane && rplane->poll_running_) {
       rplane->EnqueueLocal(std::move(msg), bytes);
       return;
@@ -743,13 +812,20 @@ void GpuPlane::DeliverLocal(Postoffice* lpo, Message& msg, int64_t bytes) {
     XPS_CHECK(!InCustomerHandler())
         << "in-handler local send needs the receiver's poll thread";
   }
+  HandToVan(van, msg, bytes, true);
+}
+
+void GpuPlane::HandToVan(Van* van, Message& msg, int64_t bytes, bool count_refs) {
   van->recv_bytes_ += bytes;
   // blobs handed over by reference in one address space = zero-copy
   // reception (the transport-level analog of the reference's
-  // registered-buffer pointer-equality assertion)
-  for (auto& d : msg.data) {
-    if (d.size() && (d.on_device() || d.size() > kInlineMax)) {
-      g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
+  // registered-buffer pointer-equality assertion). The ring path counts
+  // its own while it resolves them.
+  if (count_refs) {
+    for (auto& d : msg.data) {
+      if (d.size() && (d.on_device() || d.size() > kInlineMax)) {
+        g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
+      }
     }
   }
   if (inline_deliver_) {
@@ -757,6 +833,25 @@ void GpuPlane::DeliverLocal(Postoffice* lpo, Message& msg, int64_t bytes) {
   } else {
     van->Deliver(std::move(msg));
   }
+}
+
+GpuPlane* GpuPlane::OneSidedOwner(Peer* p, Postoffice** elpo) {
+  *elpo = LocalPeer(p);
+  if (!*elpo) return EnsureRing(p) ? this : nullptr;
+  // Cross-process the one-sided write removes the server-side launch
+  // entirely (2012 -> 2603 GB/s on the 2-joint-procs-1-GPU config). For a
+  // SAME-process peer it is measured SLOWER (61 vs 84 GB/s per-key 1 MB,
+  // RTT 50 vs 42 us, same-box A/B: the app thread becomes the single
+  // launch lane) — default off locally; XPS_LOCAL_ONE_SIDED=1 re-enables
+  // it (the write then runs on the RECEIVER plane's stream for us, so
+  // ordering stays stream-based).
+  static const bool local_one_sided =
+      Environment::Get()->GetInt("XPS_LOCAL_ONE_SIDED", 0) != 0;
+  return local_one_sided ? PlaneOf(*elpo) : nullptr;
+}
+
+hipStream_t GpuPlane::OneSidedLane(GpuPlane* owner, Peer* p) {
+  return owner == this ? StreamForPeer(p->node.id) : owner->StreamForPeer(po_->node_id());
 }
 
 bool GpuPlane::LocalPullRead(int peer_id, void* dst, uint64_t entry_off, size_t len,
@@ -768,34 +863,27 @@ bool GpuPlane::LocalPullRead(int peer_id, void* dst, uint64_t entry_off, size_t 
   XPS_STAGE(local_pull_read);
   // lane 0 of the stream our entry pushes used: for a same-process peer
   // that is the RECEIVER plane's stream for us (also the stream its
-  // handler kernels run on), else our own per-peer stream
-  hipStream_t stream;
+  // handler kernels run on), else our own per-peer stream. Not
+  // OneSidedOwner's rule: a read needs neither XPS_LOCAL_ONE_SIDED nor
+  // the peer's ring, and has a condition of its own.
+  GpuPlane* owner = this;
   if (Postoffice* elpo = LocalPeer(p)) {
-    auto* rplane = dynamic_cast<GpuPlane*>(elpo->van() ? elpo->van()->plane() : nullptr);
-    if (!rplane) return false;
+    owner = PlaneOf(elpo);
+    if (!owner) return false;
     // ordering relies on the preceding LOCAL push's kernel being
     // enqueued on this same stream BEFORE we enqueue the read — true
     // only with synchronous inline request delivery (the default). With
     // queued delivery the push launch races us: fall back to a normal
     // pull request, which the seq gate orders.
-    static const bool queue_req = Environment::Get()->GetInt("XPS_LOCAL_QUEUE_REQ", 0) != 0;
-    if (!inline_deliver_ || queue_req) return false;
-    stream = rplane->StreamForPeer(po_->node_id());
-  } else {
-    stream = StreamForPeer(peer_id);
+    if (!inline_deliver_ || LocalQueueReq()) return false;
   }
+  hipStream_t stream = OneSidedLane(owner, p);
   XPS_HIP_CHECK(hipSetDevice(device_));
   kern::DenseAssign(dst, src, len, stream);
   g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-  hipEvent_t ev = GetEvent();
-  XPS_HIP_CHECK(hipEventRecord(ev, stream));
   int64_t bytes = static_cast<int64_t>(len) + 64;
-  {
-    std::lock_guard<std::mutex> lk(pend_mu_);
-    pending_[peer_id].push_back(Pending{ev, peer_id, std::string(), std::move(resp), Message(),
-                                        bytes, po_});
-  }
-  pending_count_.fetch_add(1);
+  // the response is delivered to OURSELVES
+  Defer(p, stream, nullptr, {.resend = std::move(resp), .bytes = bytes, .local_po = po_});
   p->rx_bytes.fetch_add(bytes, std::memory_order_relaxed);
   return true;
 }
@@ -803,15 +891,9 @@ bool GpuPlane::LocalPullRead(int peer_id, void* dst, uint64_t entry_off, size_t 
 bool GpuPlane::EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out) {
   if (!FusedAssignEnabled()) return false;
   if (!(msg.meta.option & kOptPullAddr) || (msg.meta.option & kOptHostAddr)) return false;
-  static const bool local_one_sided =
-      Environment::Get()->GetInt("XPS_LOCAL_ONE_SIDED", 0) != 0;
-  // same-process peers stay on the handler's launch lane by default (see
-  // the kOptEntryPush block in Send for the measurement)
-  Postoffice* elpo = LocalPeer(p);
-  GpuPlane* rplane =
-      elpo ? dynamic_cast<GpuPlane*>(elpo->van() ? elpo->van()->plane() : nullptr) : nullptr;
-  bool can = elpo ? (local_one_sided && rplane != nullptr) : EnsureRing(p);
-  if (!can) return false;
+  Postoffice* elpo = nullptr;
+  GpuPlane* owner = OneSidedOwner(p, &elpo);
+  if (!owner) return false;
   SArray<char> vals = msg.data[1];
   size_t len = vals.size();
   if (len == 0) return false;
@@ -832,43 +914,20 @@ bool GpuPlane::EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out) {
   if (!elpo && co_one_sided) cev = CoAppend(p, kern::Seg2{entry, dst, vals.data(), len});
   hipStream_t stream = nullptr;
   if (!cev) {
-    stream = elpo ? rplane->StreamForPeer(po_->node_id()) : StreamForPeer(p->node.id);
+    stream = OneSidedLane(owner, p);
     XPS_HIP_CHECK(hipSetDevice(device_));
     kern::DenseAssign2(entry, dst, vals.data(), len, stream);
     g_fused_launches.fetch_add(1, std::memory_order_relaxed);
   }
   g_fused_assign.fetch_add(1, std::memory_order_relaxed);
   g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-  Message meta_msg;
-  meta_msg.meta = msg.meta;
-  meta_msg.meta.option |= kOptInPlace;
-  meta_msg.meta.val_len = static_cast<int64_t>(len);
-  meta_msg.meta.data_type.clear();
-  for (size_t i = 0; i < msg.data.size(); ++i) {
-    if (i == 1 || msg.data[i].on_device()) continue;
-    meta_msg.data.push_back(msg.data[i]);
-    meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-  }
-  int64_t bytes = 64 + static_cast<int64_t>(len);
-  Message keepalive;
-  keepalive.data.push_back(vals);
+  Message note = InPlaceNote(msg, len);
   std::string payload;
-  if (!elpo) {
-    std::vector<char> br(meta_msg.data.size(), 0);
-    XPS_CHECK(Serialize(meta_msg, br, &payload));
-  }
-  hipEvent_t ev = nullptr;
-  if (!cev) {
-    ev = GetEvent();
-    XPS_HIP_CHECK(hipEventRecord(ev, stream));
-  }
-  {
-    std::lock_guard<std::mutex> lk(pend_mu_);
-    pending_[p->node.id].push_back(Pending{ev, p->node.id, std::move(payload),
-                                           std::move(meta_msg), std::move(keepalive), bytes,
-                                           elpo, std::move(cev)});
-  }
-  pending_count_.fetch_add(1);
+  if (!elpo) SerializeNote(&note, /*may_drop_blobs=*/false, &payload);
+  int64_t bytes = 64 + static_cast<int64_t>(len);
+  Defer(p, stream, std::move(cev),
+        {.payload = std::move(payload), .resend = std::move(note),
+         .keepalive = KeepAlive(vals), .bytes = bytes, .local_po = elpo});
   p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
   *bytes_out = bytes;
   return true;
@@ -888,121 +947,124 @@ void GpuPlane::EnqueueLocal(Message msg, int64_t bytes) {
 // thread — a direct call, with GPU completion still gated by the lane
 // event for responses (the requester's buffers must not be released
 // before the kernels that read/write them finish).
+hipStream_t GpuPlane::ResponseLane(const Message& msg, int peer_id) {
+  return (msg.meta.option & kOptPullLane) ? PullStreamForPeer(peer_id) : StreamForPeer(peer_id);
+}
+
+void GpuPlane::DrainLanes(int peer_id) {
+  for (int l = 0; l < lanes_; ++l) (void)hipStreamSynchronize(StreamLane(peer_id, l));
+}
+
+bool GpuPlane::DefersResponse(const Message& msg) const {
+  return !msg.meta.request && device_ >= 0 && !KernelLessAck(msg);
+}
+
+bool GpuPlane::CopyToHostDest(Peer* p, uint64_t addr, const SArray<char>& vals) {
+  void* base = HostShmPool::MapPeer(p->node.host_pool_uid, p->node.host_pool_capacity);
+  if (!base || addr > p->node.host_pool_capacity ||
+      vals.size() > p->node.host_pool_capacity - addr) {
+    return false;
+  }
+  HostPar::CopyBytes(static_cast<char*>(base) + addr, vals.data(), vals.size());
+  return true;
+}
+
+hipStream_t GpuPlane::WriteHbmDest(Peer* p, const Message& msg, const SArray<char>& vals) {
+  char* dst = ResolvePeer(p, msg.meta.addr, vals.size());
+  if (!dst) {
+    DrainLanes(p->node.id);
+    return nullptr;
+  }
+  hipStream_t stream = ResponseLane(msg, p->node.id);
+  XPS_HIP_CHECK(hipSetDevice(device_));
+  // copy KERNEL instead of hipMemcpyAsync: measured 5.2 vs 4.85 TB/s
+  // same-device, and it reads/writes hipIpc-mapped peer memory alike
+  kern::DenseAssign(dst, vals.data(), vals.size(), stream);
+  return stream;
+}
+
+void GpuPlane::SerializeNote(Message* note, bool may_drop_blobs, std::string* payload) {
+  std::vector<char> all_inline(note->data.size(), 0);
+  if (Serialize(*note, all_inline, payload)) return;
+  XPS_CHECK(may_drop_blobs) << "in-place note does not fit the ring";
+  note->data.clear();
+  note->meta.data_type.clear();
+  XPS_CHECK(Serialize(*note, {}, payload));
+}
+
+void GpuPlane::Defer(Peer* p, hipStream_t stream, std::shared_ptr<CoEvent> cev, Pending pd) {
+  XPS_STAGE(defer_queue);
+  XPS_CHECK_GE(device_, 0) << "deferred sends are a GPU-plane feature";
+  if (!cev) {
+    XPS_HIP_CHECK(hipSetDevice(device_));
+    pd.ev = GetEvent();
+    XPS_HIP_CHECK(hipEventRecord(pd.ev, stream));
+  }
+  int peer_id = p->node.id;
+  pd.peer_id = peer_id;
+  pd.cev = std::move(cev);
+  {
+    std::lock_guard<std::mutex> lk(pend_mu_);
+    pending_[peer_id].push_back(std::move(pd));
+  }
+  pending_count_.fetch_add(1);
+  XPS_VLOG(3) << "deferred send queued -> " << peer_id;
+}
+
+// Same-process fast path (joint mode: worker + co-located server share
+// the process). This is the reference's IPCTransport/shared_node_mapping_
+// locality taken to its limit: no serialization, no ring hop, no poll
+// thread — a direct call, with GPU completion still gated by the lane
+// event for responses (the requester's buffers must not be released
+// before the kernels that read/write them finish).
 int64_t GpuPlane::SendLocal(Message& msg, Peer* p, Postoffice* lpo) {
   XPS_STAGE(plane_send_local);
-  bool response = !msg.meta.request;
   int64_t bytes = 64;
   for (auto& d : msg.data) bytes += static_cast<int64_t>(d.size());
 
-  // ---- pull response, HOST vals + advertised HOST destination: copy
-  // into the requester's buffer NOW (the synchronous-handler contract —
-  // the store may mutate right after Response returns), meta-only after
-  if (response && msg.meta.pull && msg.data.size() > 1 && !msg.data[1].on_device() &&
-      msg.data[1].size() > 0 && (msg.meta.option & kOptPullAddr) &&
-      (msg.meta.option & kOptHostAddr)) {
-    void* base = HostShmPool::MapPeer(p->node.host_pool_uid, p->node.host_pool_capacity);
+  if (HasPullDest(msg)) {
     SArray<char> vals = msg.data[1];
-    if (base && msg.meta.addr <= p->node.host_pool_capacity &&
-        vals.size() <= p->node.host_pool_capacity - msg.meta.addr) {
-      HostPar::CopyBytes(static_cast<char*>(base) + msg.meta.addr, vals.data(), vals.size());
+    // host destination: copy into the requester's buffer NOW, note after
+    // (a destination that cannot be mapped takes the plain path below)
+    if (HostDest(msg) && CopyToHostDest(p, msg.meta.addr, vals)) {
       g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-      Message meta_msg;
-      meta_msg.meta = msg.meta;
-      meta_msg.meta.option |= kOptInPlace;
-      meta_msg.meta.val_len = static_cast<int64_t>(vals.size());
-      meta_msg.meta.data_type.clear();
-      for (size_t i = 0; i < msg.data.size(); ++i) {
-        if (i == 1 || msg.data[i].on_device()) continue;
-        SArray<char> copy(msg.data[i].size());  // snapshot small keys/lens too
-        memcpy(copy.data(), msg.data[i].data(), msg.data[i].size());
-        meta_msg.data.push_back(copy);
-        meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-      }
-      DeliverLocal(lpo, meta_msg, bytes);
+      Message note = InPlaceNote(msg, vals.size(), NoteBlobs::kSnapshot);
+      DeliverLocal(lpo, note, bytes);
+      p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
+      return bytes;
+    }
+    // HBM destination: run the in-place write now, deliver the note once
+    // the copy completes
+    if (HbmDest(msg)) {
+      hipStream_t stream = WriteHbmDest(p, msg, vals);
+      if (!stream) return -1;  // TCP fallback (streams drained first)
+      g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
+      Message note = InPlaceNote(msg, vals.size());
+      msg.data.clear();
+      Defer(p, stream, nullptr,
+            {.resend = std::move(note), .keepalive = KeepAlive(vals), .bytes = bytes,
+             .local_po = lpo});
       p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
       return bytes;
     }
   }
 
-  // device-vals pull response with an advertised HBM destination: run
-  // the in-place write now, deliver the meta once the copy completes
-  if (response && msg.meta.pull && msg.data.size() > 1 && msg.data[1].on_device() &&
-      (msg.meta.option & kOptPullAddr) && !(msg.meta.option & kOptHostAddr)) {
-    SArray<char> vals = msg.data[1];
-    char* dst = ResolvePeer(p, msg.meta.addr, vals.size());
-    if (!dst) {
-      for (int l = 0; l < lanes_; ++l) (void)hipStreamSynchronize(StreamLane(p->node.id, l));
-      return -1;  // TCP fallback (streams drained first)
-    }
-    hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(p->node.id)
-                                                          : StreamForPeer(p->node.id);
-    XPS_HIP_CHECK(hipSetDevice(device_));
-    kern::DenseAssign(dst, vals.data(), vals.size(), stream);
-    g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-    Message meta_msg;
-    meta_msg.meta = msg.meta;
-    meta_msg.meta.option |= kOptInPlace;
-    meta_msg.meta.val_len = static_cast<int64_t>(vals.size());
-    meta_msg.meta.data_type.clear();
-    for (size_t i = 0; i < msg.data.size(); ++i) {
-      if (i == 1 || msg.data[i].on_device()) continue;
-      meta_msg.data.push_back(msg.data[i]);
-      meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-    }
-    msg.data.clear();
-    Message keepalive;
-    keepalive.data.push_back(vals);
-    hipEvent_t ev = GetEvent();
-    XPS_HIP_CHECK(hipEventRecord(ev, stream));
-    {
-      std::lock_guard<std::mutex> lk(pend_mu_);
-      pending_[p->node.id].push_back(Pending{ev, p->node.id, std::string(),
-                                             std::move(meta_msg), std::move(keepalive), bytes,
-                                             lpo});
-    }
-    pending_count_.fetch_add(1);
-    p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
-    return bytes;
-  }
-
-  // ack of a one-sided push: the handler launched nothing for it — no
-  // event to wait, deliver right away
-  bool kernel_less_ack = KernelLessAck(msg);
-  if (response && device_ >= 0 && !kernel_less_ack) {
+  if (DefersResponse(msg)) {
     // GPU handler output: deliver once this peer's lane drained
     XPS_STAGE(local_defer);
     // the handler's coalesced dual write: no event of its own, the entry
     // waits for the shared event of its batch
     std::shared_ptr<CoEvent> cev = TakeTicket(p->node.id);
-    hipEvent_t ev = nullptr;
-    if (!cev) {
-      hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(p->node.id)
-                                                            : StreamForPeer(p->node.id);
-      ev = GetEvent();
-      XPS_HIP_CHECK(hipSetDevice(device_));
-      XPS_HIP_CHECK(hipEventRecord(ev, stream));
-    }
-    Message resend = msg;
-    {
-      std::lock_guard<std::mutex> lk(pend_mu_);
-      pending_[p->node.id].push_back(Pending{ev, p->node.id, std::string(), std::move(resend),
-                                             Message(), bytes, lpo, std::move(cev)});
-    }
-    pending_count_.fetch_add(1);
+    hipStream_t stream = cev ? nullptr : ResponseLane(msg, p->node.id);
+    Defer(p, stream, std::move(cev), {.resend = msg, .bytes = bytes, .local_po = lpo});
   } else {
+    // requests, kernel-less acks and every send of a host-only plane go
+    // out now. Requests need no copy: the sender's buffers are pinned
+    // until the response arrives.
     Message copy = msg;
-    if (response) {
-      // synchronous (host) handler responses may be VIEWS of mutable
-      // server state — the old wire paths serialized them before the
-      // handler could mutate again; snapshot host blobs to keep that
-      // contract (requests need no copy: the sender's buffers are
-      // pinned until the response arrives)
+    if (!msg.meta.request) {
       for (auto& d : copy.data) {
-        if (!d.on_device() && d.size()) {
-          SArray<char> snap(d.size());
-          memcpy(snap.data(), d.data(), d.size());
-          d = snap;
-        }
+        if (!d.on_device() && d.size()) d = Snapshot(d);
       }
     }
     DeliverLocal(lpo, copy, bytes);
@@ -1025,58 +1087,26 @@ int64_t GpuPlane::Send(Message& msg, const Node& peer_node) {
   // 356): the worker writes the server's advertised store entry with
   // ITS OWN kernel and sends the meta-only notification once the write
   // completes. The server's push handling shrinks to an ack.
-  static const bool local_one_sided =
-      Environment::Get()->GetInt("XPS_LOCAL_ONE_SIDED", 0) != 0;
   if (msg.meta.request && msg.meta.push && !msg.meta.pull &&
       (msg.meta.option & kOptEntryPush) && device_ >= 0 && msg.data.size() > 1 &&
       msg.data[1].on_device()) {
-    // Cross-process this removes the server-side launch entirely
-    // (2012 -> 2603 GB/s on the 2-joint-procs-1-GPU config). For a
-    // SAME-process peer it is measured SLOWER (61 vs 84 GB/s per-key
-    // 1 MB, RTT 50 vs 42 us, same-box A/B: the app thread becomes the
-    // single launch lane) — default off locally; XPS_LOCAL_ONE_SIDED=1
-    // re-enables it (the write then runs on the RECEIVER plane's stream
-    // for us, so ordering stays stream-based).
-    Postoffice* elpo = LocalPeer(p);
-    GpuPlane* rplane =
-        elpo ? dynamic_cast<GpuPlane*>(elpo->van() ? elpo->van()->plane() : nullptr) : nullptr;
-    bool can = elpo ? (local_one_sided && rplane != nullptr) : EnsureRing(p);
+    Postoffice* elpo = nullptr;
+    GpuPlane* owner = OneSidedOwner(p, &elpo);
     SArray<char> vals = msg.data[1];
-    char* dst = can ? ResolvePeer(p, msg.meta.addr, vals.size()) : nullptr;
+    char* dst = owner ? ResolvePeer(p, msg.meta.addr, vals.size()) : nullptr;
     if (dst) {
       XPS_STAGE(entry_push);
-      hipStream_t stream = elpo ? rplane->StreamForPeer(po_->node_id())
-                                : StreamForPeer(p->node.id);
+      hipStream_t stream = OneSidedLane(owner, p);
       XPS_HIP_CHECK(hipSetDevice(device_));
       kern::DenseAssign(dst, vals.data(), vals.size(), stream);
       g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-      Message meta_msg;
-      meta_msg.meta = msg.meta;
-      meta_msg.meta.option |= kOptInPlace;
-      meta_msg.meta.val_len = static_cast<int64_t>(vals.size());
-      meta_msg.meta.data_type.clear();
-      for (size_t i = 0; i < msg.data.size(); ++i) {
-        if (i == 1 || msg.data[i].on_device()) continue;
-        meta_msg.data.push_back(msg.data[i]);
-        meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-      }
-      int64_t bytes = 64 + static_cast<int64_t>(vals.size());
-      Message keepalive;
-      keepalive.data.push_back(vals);
+      Message note = InPlaceNote(msg, vals.size());
       std::string payload;
-      if (!elpo) {
-        std::vector<char> br(meta_msg.data.size(), 0);
-        XPS_CHECK(Serialize(meta_msg, br, &payload));
-      }
-      hipEvent_t ev = GetEvent();
-      XPS_HIP_CHECK(hipEventRecord(ev, stream));
-      {
-        std::lock_guard<std::mutex> lk(pend_mu_);
-        pending_[p->node.id].push_back(Pending{ev, p->node.id, std::move(payload),
-                                               std::move(meta_msg), std::move(keepalive),
-                                               bytes, elpo});
-      }
-      pending_count_.fetch_add(1);
+      if (!elpo) SerializeNote(&note, /*may_drop_blobs=*/false, &payload);
+      int64_t bytes = 64 + static_cast<int64_t>(vals.size());
+      Defer(p, stream, nullptr,
+            {.payload = std::move(payload), .resend = std::move(note),
+             .keepalive = KeepAlive(vals), .bytes = bytes, .local_po = elpo});
       p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
       return bytes;
     }
@@ -1099,97 +1129,43 @@ int64_t GpuPlane::Send(Message& msg, const Node& peer_node) {
 
   if (Postoffice* lpo = LocalPeer(p)) return SendLocal(msg, p, lpo);
   bool response = !msg.meta.request;
-  auto sync_peer_lanes = [this, &peer_node] {
-    for (int l = 0; l < lanes_; ++l) (void)hipStreamSynchronize(StreamLane(peer_node.id, l));
-  };
   if (!EnsureRing(p)) {
-    // TCP fallback for a response must not outrun handler kernels still
-    // running on this peer's streams (the worker may reuse buffers on ack)
-    if (response && device_ >= 0) sync_peer_lanes();
+    if (response && device_ >= 0) DrainLanes(peer_node.id);
     return -1;
   }
 
-  // ---- pull response with HOST vals + host destination: memcpy now --
-  if (response && msg.meta.pull && msg.data.size() > 1 && !msg.data[1].on_device() &&
-      msg.data[1].size() > 0 && (msg.meta.option & kOptPullAddr) &&
-      (msg.meta.option & kOptHostAddr)) {
-    void* base = HostShmPool::MapPeer(p->node.host_pool_uid, p->node.host_pool_capacity);
+  if (HasPullDest(msg)) {
     SArray<char> vals = msg.data[1];
-    if (base && msg.meta.addr <= p->node.host_pool_capacity &&
-        vals.size() <= p->node.host_pool_capacity - msg.meta.addr) {
-      HostPar::CopyBytes(static_cast<char*>(base) + msg.meta.addr, vals.data(), vals.size());
-      Message meta_msg;
-      meta_msg.meta = msg.meta;
-      meta_msg.meta.option |= kOptInPlace;
-      meta_msg.meta.val_len = static_cast<int64_t>(vals.size());
-      for (size_t i = 0; i < msg.data.size(); ++i) {
-        if (i == 1 || msg.data[i].on_device() || msg.data[i].size() > kInlineMax) continue;
-        meta_msg.data.push_back(msg.data[i]);
-        meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-      }
-      std::vector<char> br(meta_msg.data.size(), 0);
+    // host destination: memcpy now, then the note over the ring
+    if (HostDest(msg)) {
+      if (!CopyToHostDest(p, msg.meta.addr, vals)) return -1;  // unmappable: TCP fallback
+      Message note = InPlaceNote(msg, vals.size(), NoteBlobs::kInlineOnly);
       std::string payload;
-      if (!Serialize(meta_msg, br, &payload)) {
-        meta_msg.data.clear();
-        meta_msg.meta.data_type.clear();
-        XPS_CHECK(Serialize(meta_msg, {}, &payload));
-      }
+      SerializeNote(&note, /*may_drop_blobs=*/true, &payload);
       int64_t bytes = static_cast<int64_t>(vals.size() + payload.size());
       auto ring = RingOf(p);
       if (!ring || !ring->Push(payload.data(), static_cast<uint32_t>(payload.size()))) return -1;
       p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
       return bytes;
     }
-    return -1;  // cannot map the destination: TCP fallback
-  }
-
-  // ---- pull response with device vals: one-sided xGMI write ----------
-  if (response && msg.meta.pull && msg.data.size() > 1 && msg.data[1].on_device() &&
-      (msg.meta.option & kOptPullAddr)) {
-    SArray<char> vals = msg.data[1];
-    char* dst = ResolvePeer(p, msg.meta.addr, vals.size());
-    if (!dst) {
-      sync_peer_lanes();
-      return -1;  // TCP fallback (streams drained first)
+    // HBM destination: one-sided xGMI write, the note follows its event
+    if (HbmDest(msg)) {
+      hipStream_t stream = WriteHbmDest(p, msg, vals);
+      if (!stream) return -1;  // TCP fallback (streams drained first)
+      Message note = InPlaceNote(msg, vals.size());
+      std::string payload;
+      SerializeNote(&note, /*may_drop_blobs=*/true, &payload);
+      int64_t bytes = static_cast<int64_t>(vals.size() + payload.size());
+      msg.data.clear();
+      // The note is also the TCP-resendable form: by the time a fallback
+      // happens the event has fired, i.e. the in-place write already
+      // landed in the peer's pool.
+      Defer(p, stream, nullptr,
+            {.payload = std::move(payload), .resend = std::move(note),
+             .keepalive = KeepAlive(vals), .bytes = bytes});
+      p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
+      return bytes;
     }
-    // pull lane (only when the handler prepared its ordering there): the
-    // response copy overlaps the next push kernel on lane 0
-    hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(peer_node.id)
-                                                          : StreamForPeer(peer_node.id);
-    XPS_HIP_CHECK(hipSetDevice(device_));
-    // copy KERNEL instead of hipMemcpyAsync: measured 5.2 vs 4.85 TB/s
-    // same-device, and it reads/writes hipIpc-mapped peer memory alike
-    kern::DenseAssign(dst, vals.data(), vals.size(), stream);
-    Message meta_msg;
-    meta_msg.meta = msg.meta;
-    meta_msg.meta.option |= kOptInPlace;
-    meta_msg.meta.val_len = static_cast<int64_t>(vals.size());
-    meta_msg.meta.data_type.clear();
-    // keep host-side keys/lens blobs for the merge bookkeeping
-    for (size_t i = 0; i < msg.data.size(); ++i) {
-      if (i == 1 || msg.data[i].on_device()) continue;
-      meta_msg.data.push_back(msg.data[i]);
-      meta_msg.meta.data_type.push_back(msg.meta.data_type[i]);
-    }
-    std::vector<char> by_ref(meta_msg.data.size(), 0);
-    std::string payload;
-    if (!Serialize(meta_msg, by_ref, &payload)) {
-      meta_msg.data.clear();
-      meta_msg.meta.data_type.clear();
-      XPS_CHECK(Serialize(meta_msg, {}, &payload));
-    }
-    int64_t bytes = static_cast<int64_t>(vals.size() + payload.size());
-    msg.data.clear();
-    // the original msg owns vals; keep it alive until the event fires.
-    // meta_msg (kOptInPlace, host blobs only) is the TCP-resendable form:
-    // by the time a fallback happens the event has fired, i.e. the
-    // in-place write already landed in the peer's pool.
-    Message keepalive;
-    keepalive.data.push_back(vals);
-    DeferSendInternal(p, peer_node.id, stream, std::move(meta_msg), std::move(keepalive),
-                      std::move(payload), bytes);
-    p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
-    return bytes;
   }
 
   // ---- general path: inline blobs + by-ref device/host-pool blobs ----
@@ -1211,42 +1187,21 @@ int64_t GpuPlane::Send(Message& msg, const Node& peer_node) {
     return -1;
   }
   int64_t bytes = static_cast<int64_t>(payload.size()) + ref_bytes;
-  // ack of a one-sided push: the handler launched nothing — no event
-  bool kernel_less_ack = KernelLessAck(msg);
-  if (response && device_ >= 0 && !kernel_less_ack) {
-    // order behind any handler kernels on this peer's lane (the handler
-    // flags pull-lane work via kOptPullLane; everything else is lane 0).
-    // The resend copy doubles as the keepalive (shallow: SArrays shared).
-    hipStream_t stream = (msg.meta.option & kOptPullLane) ? PullStreamForPeer(peer_node.id)
-                                                          : StreamForPeer(peer_node.id);
-    Message resend = msg;
-    DeferSendInternal(p, peer_node.id, stream, std::move(resend), Message(), std::move(payload),
-                      bytes);
+  if (DefersResponse(msg)) {
+    // order behind any handler kernels on this peer's lane. The resend
+    // copy doubles as the keepalive (shallow: SArrays shared).
+    Defer(p, ResponseLane(msg, peer_node.id), nullptr,
+          {.payload = std::move(payload), .resend = msg, .bytes = bytes});
   } else {
-    // requests — and every send of a host-only plane — go out now (host
-    // responses were produced synchronously; nothing to wait for)
+    // requests, kernel-less acks and every send of a host-only plane go
+    // out now (host responses were produced synchronously; nothing to
+    // wait for)
     auto ring = RingOf(p);
     if (!ring || !ring->Push(payload.data(), static_cast<uint32_t>(payload.size()))) return -1;
     XPS_VLOG(3) << "plane send done -> " << peer_node.id;
   }
   p->tx_bytes.fetch_add(bytes, std::memory_order_relaxed);
   return bytes;
-}
-
-void GpuPlane::DeferSendInternal(Peer* p, int peer_id, hipStream_t stream, Message resend,
-                                 Message keepalive, std::string payload, int64_t bytes) {
-  XPS_STAGE(defer_queue);
-  XPS_CHECK_GE(device_, 0) << "deferred sends are a GPU-plane feature";
-  hipEvent_t ev = GetEvent();
-  XPS_HIP_CHECK(hipSetDevice(device_));
-  XPS_HIP_CHECK(hipEventRecord(ev, stream));
-  {
-    std::lock_guard<std::mutex> lk(pend_mu_);
-    pending_[peer_id].push_back(Pending{ev, peer_id, std::move(payload), std::move(resend),
-                                        std::move(keepalive), bytes});
-  }
-  pending_count_.fetch_add(1);
-  XPS_VLOG(3) << "deferred send queued -> " << peer_id;
 }
 
 void GpuPlane::CompletionLoop() {
@@ -1366,17 +1321,7 @@ void GpuPlane::RingPollLoop() {
       local_count_.fetch_sub(static_cast<int>(local.size()));
       for (auto& lm : local) {
         XPS_STAGE(local_handle);
-        po_->van()->recv_bytes_ += lm.second;
-        for (auto& d : lm.first.data) {
-          if (d.size() && (d.on_device() || d.size() > kInlineMax)) {
-            g_zero_copy_recv.fetch_add(1, std::memory_order_relaxed);
-          }
-        }
-        if (inline_deliver_) {
-          po_->van()->DeliverInline(lm.first);
-        } else {
-          po_->van()->Deliver(std::move(lm.first));
-        }
+        HandToVan(po_->van(), lm.first, lm.second, true);
       }
       idle = 0;
       local.clear();
@@ -1441,15 +1386,11 @@ void GpuPlane::RingPollLoop() {
     }
     if (!ok) continue;
     XPS_VLOG(3) << "ring recv: " << msg.DebugString();
-    po_->van()->recv_bytes_ += n + ref_bytes;
     if (msg.meta.sender != kEmptyNodeID) {
       GetPeer(msg.meta.sender)->rx_bytes.fetch_add(n + ref_bytes, std::memory_order_relaxed);
     }
-    if (inline_deliver_) {
-      po_->van()->DeliverInline(msg);
-    } else {
-      po_->van()->Deliver(std::move(msg));
-    }
+    // by-reference blobs were counted above, while they were resolved
+    HandToVan(po_->van(), msg, n + ref_bytes, false);
   }
 }
 

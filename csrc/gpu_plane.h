@@ -162,10 +162,12 @@ class GpuPlane : public DataPlane {
     std::mutex mu;
   };
 
+  // one message waiting for GPU work; the call sites of Defer name the
+  // fields they set, Defer fills ev, peer_id and cev
   struct Pending {
-    hipEvent_t ev;  // null when cev is set
-    int peer_id;
-    std::string payload;
+    hipEvent_t ev = nullptr;  // null when cev is set
+    int peer_id = 0;
+    std::string payload;  // serialized ring form (empty for local_po)
     // TCP-resendable form of this message: if the ring push fails after
     // the event fires, the van sends this instead (never drop a response
     // — the requester is blocked in Wait). For in-place writes this is
@@ -173,7 +175,7 @@ class GpuPlane : public DataPlane {
     // For same-process peers it is the message delivered directly.
     Message resend;
     Message keepalive;  // holds pool temporaries until the event fires
-    int64_t bytes;
+    int64_t bytes = 0;
     Postoffice* local_po = nullptr;  // same-process: deliver, don't ring-push
     std::shared_ptr<CoEvent> cev;    // coalesced launch this entry waits for
   };
@@ -226,8 +228,42 @@ class GpuPlane : public DataPlane {
   // Returns false — nothing launched, nothing queued — when the entry or
   // the destination cannot be resolved or the peer has no ring.
   bool EntryPushPull(Message& msg, Peer* p, int64_t* bytes_out);
-  void DeferSendInternal(Peer* p, int peer_id, hipStream_t stream, Message resend,
-                         Message keepalive, std::string payload, int64_t bytes);
+  // ---- the delivery rules of the send paths, each stated once --------
+  // Queue `pd` until the work now on `stream` completed: record a pooled
+  // event there — or wait on `cev`, the shared event of the coalesced
+  // launch that carries this message's write (stream unused then).
+  void Defer(Peer* p, hipStream_t stream, std::shared_ptr<CoEvent> cev, Pending pd);
+  // Ring form of an in-place note, every blob inline. A note that
+  // outgrows the ring sheds its blobs and travels as bare meta when
+  // `may_drop_blobs`; otherwise not fitting is a bug.
+  void SerializeNote(Message* note, bool may_drop_blobs, std::string* payload);
+  // the lane a handler's response is ordered on: the pull lane when the
+  // handler prepared its ordering there (kOptPullLane: the response copy
+  // then overlaps the next push kernel on lane 0), else lane 0
+  hipStream_t ResponseLane(const Message& msg, int peer_id);
+  // copy host vals to offset `addr` of the requester's mapped host pool;
+  // false when the pool cannot be mapped or the range leaves it
+  bool CopyToHostDest(Peer* p, uint64_t addr, const SArray<char>& vals);
+  // launch the copy of device vals into the HBM destination that pull
+  // response `msg` answers, on its ResponseLane. nullptr: destination not
+  // mapped — the peer's lanes were drained for the TCP fallback.
+  hipStream_t WriteHbmDest(Peer* p, const Message& msg, const SArray<char>& vals);
+  // Which plane's lane 0 carries OUR one-sided write to p's store, and
+  // may it run at all (nullptr = no)? Cross-process: this plane, once
+  // the peer's ring is up. Same process (*elpo set): the receiver's
+  // plane, and only with XPS_LOCAL_ONE_SIDED=1.
+  GpuPlane* OneSidedOwner(Peer* p, Postoffice** elpo);
+  // that lane: taken only when the write is launched, because handing
+  // out lane 0 launches its open batch
+  hipStream_t OneSidedLane(GpuPlane* owner, Peer* p);
+  // account a received message and hand it to the van; count_refs: count
+  // its by-reference blobs as zero-copy receptions here
+  void HandToVan(Van* van, Message& msg, int64_t bytes, bool count_refs);
+  // a TCP fallback must not outrun kernels still running on this peer's
+  // streams (the worker may reuse its buffers on the ack): drain them
+  void DrainLanes(int peer_id);
+  // a GPU handler's response waits for the handler's kernels
+  bool DefersResponse(const Message& msg) const;
 
   Postoffice* po_;
   int device_;

@@ -148,6 +148,34 @@ def test_fused_switch_off_in_child():
     assert deltas == [0, 0, 0, 0] and total == 0
 
 
+def _local_one_sided_worker_fn(ps_mod, rank):
+    server = ps_mod.KVServer(0)
+    server.set_gpu_dense_handle(mode="assign")
+    worker = ps_mod.KVWorker(0, 0)
+    deltas = _fused_rounds(ps_mod, worker)
+    # plain one-sided push, then pull, of a tiny and of a larger key
+    for key, n in ((320, 3), (321, 1024)):
+        keys = np.array([key], dtype=np.uint64)
+        lens = np.array([n], dtype=np.int32)
+        src, dst = ps_mod.pool_alloc(n * 4), ps_mod.pool_alloc(n * 4)
+        for rep in range(2):  # the second push of a key is the one-sided one
+            vals = np.arange(n, dtype=np.float32) * 0.75 - 5.0 + 100.0 * rep
+            src.copy_from(vals)
+            worker.wait(worker.zpush_ptr(keys, src.ptr, n * 4, 0, lens, cmd=1))
+            worker.wait(worker.zpull_ptr(keys, dst.ptr, n * 4, 0, lens, cmd=1))
+            assert np.array_equal(dst.to_numpy_f32(), vals), (key, rep)
+    return deltas, server
+
+
+def test_fused_local_one_sided_in_child():
+    """XPS_LOCAL_ONE_SIDED=1: the worker's own write to a same-process
+    server runs on the receiver plane's stream; identical values (checked
+    in the child), one dual-write launch per key once the adverts are in."""
+    results = launch_local(1, 1, _local_one_sided_worker_fn, joint=True, devices={0: 0},
+                           env_extra={"XPS_POOL_GB": 4, "XPS_LOCAL_ONE_SIDED": 1}, timeout=300)
+    assert results[0] == [0, 3, 3, 3]
+
+
 # --------------------------------------------------------------- fallbacks
 
 def test_fused_fallbacks_assign_handler():
