@@ -135,6 +135,22 @@ struct MxSeg {
 int BatchedMxAccumulate(const MxSeg* segs_host, int n, bool assign, hipStream_t s,
                         int tile_cap = 0);
 int BatchedMxFinish(const MxSeg* segs_host, int n, hipStream_t s, int tile_cap = 0);
+// Worker side over segments, one launch per kMaxBatch non-empty ones;
+// output bytes are those of MxQuantize / MxDequantize run per segment.
+// Segments must not overlap each other. A launch moves fp32 as float4 when
+// every segment in it has a 16 B-aligned f32, else element-wise. A null f32
+// on a non-empty segment is std::invalid_argument; a list without a
+// non-empty segment makes no HIP call. Both return the number of launches.
+struct MxWorkSeg {
+  float* f32;    // quantize reads it, dequantize writes it; any 4-byte offset
+  void* packed;  // 16 B-aligned; MxPackedBytes(n) bytes
+  size_t n;      // elements; any value, 0 = empty segment
+};
+// packed = Q(f32[0, n)) per segment, the last superblock zero-filled past n
+int BatchedMxQuantize(const MxWorkSeg* segs_host, int n, hipStream_t s, int tile_cap = 0);
+// f32[0, n) = D(packed) * alpha per segment: exactly n floats written
+int BatchedMxDequantize(const MxWorkSeg* segs_host, int n, float alpha, hipStream_t s,
+                        int tile_cap = 0);
 
 }  // namespace kern
 }  // namespace xps

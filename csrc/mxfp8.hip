@@ -370,6 +370,136 @@ int LaunchBatchedMx(const char* who, const MxSeg* segs_host, int n, hipStream_t 
   return launches;
 }
 
+struct MxWorkSegArray {
+  MxWorkSeg d[kMaxBatch];
+  unsigned long long prefix[kMaxBatch + 1];  // superblock offsets, prefix[n] = total
+  int n;
+};
+
+// Worker side, up to kMaxBatch segments concatenated in superblock space
+// and tiled like batched_mx_kernel: block-uniform table reads, uniform base
+// pointers in the inner loops. A segment's last superblock may be partial
+// (n is any positive count); no segment is empty.
+// kVec: every segment's f32 is 16 B-aligned
+template <bool kVec>
+__global__ void __launch_bounds__(kBlock)
+    batched_mx_quantize_kernel(MxWorkSegArray da, size_t supers_per_block) {
+  TileRunIter it = TileRunsBegin(da.prefix, da.n, supers_per_block, blockIdx.x);
+  TileRun run;
+  while (TileRunsNext(da.prefix, &it, &run)) {
+    const float* __restrict__ src = da.d[run.seg].f32;
+    uint8_t* __restrict__ packed = static_cast<uint8_t*>(da.d[run.seg].packed);
+    size_t n = da.d[run.seg].n;
+    // whole superblocks of lanes (StorePacked); a lane past n loads zeros
+    size_t end = run.hi * kSuperLanes;
+    for (size_t u = run.lo * kSuperLanes + threadIdx.x; u < end; u += kBlock) {
+      float v[kLaneElems];
+      Load16Bounded<kVec>(src, u * kLaneElems, n, v);
+      uint32_t byte;
+      uint4 codes = Quant16(v, &byte);
+      StorePacked(packed, u, codes, byte);
+    }
+  }
+}
+
+template <bool kVec>
+__global__ void __launch_bounds__(kBlock)
+    batched_mx_dequantize_kernel(MxWorkSegArray da, float alpha, size_t supers_per_block) {
+  TileRunIter it = TileRunsBegin(da.prefix, da.n, supers_per_block, blockIdx.x);
+  TileRun run;
+  while (TileRunsNext(da.prefix, &it, &run)) {
+    float* __restrict__ dst = da.d[run.seg].f32;
+    const uint8_t* __restrict__ packed = static_cast<const uint8_t*>(da.d[run.seg].packed);
+    size_t n = da.d[run.seg].n;
+    // the run's quads end with the segment's elements, not with its last
+    // superblock
+    size_t run_end = run.hi * kSuperQuads;
+    size_t quads = (n + kQuadElems - 1) / kQuadElems;
+    size_t whole = n / kQuadElems;
+    size_t end = run_end < quads ? run_end : quads;
+    size_t whole_end = run_end < whole ? run_end : whole;
+    size_t q = run.lo * kSuperQuads + threadIdx.x;
+    // a whole tile is kQuadSteps strides of the block: all of a lane's
+    // loads go out ahead of its stores
+    for (; q + (kQuadSteps - 1) * kBlock < whole_end; q += kQuadSteps * kBlock) {
+      float4 v[kQuadSteps];
+#pragma unroll
+      for (int j = 0; j < kQuadSteps; ++j) v[j] = Dequant4(packed, q + j * kBlock);
+#pragma unroll
+      for (int j = 0; j < kQuadSteps; ++j) {
+        Store4<kVec>(dst + (q + j * kBlock) * kQuadElems, Scale4(v[j], alpha));
+      }
+    }
+    for (; q < end; q += kBlock) {
+      float4 v = Scale4(Dequant4(packed, q), alpha);
+      size_t base = q * kQuadElems;
+      if (base + kQuadElems <= n) {
+        Store4<kVec>(dst + base, v);
+      } else {  // the quad that holds element n - 1: nothing is written past n
+        if (base < n) dst[base] = v.x;
+        if (base + 1 < n) dst[base + 1] = v.y;
+        if (base + 2 < n) dst[base + 2] = v.z;
+      }
+    }
+  }
+}
+
+// kQuant: batched_mx_quantize_kernel, else batched_mx_dequantize_kernel
+template <bool kQuant>
+int LaunchBatchedMxWork(const char* who, const MxWorkSeg* segs_host, int n, float alpha,
+                        hipStream_t s, int tile_cap) {
+  for (int i = 0; i < n; ++i) {
+    CheckPacked(who, segs_host[i].packed, 0);
+    if (segs_host[i].n && !segs_host[i].f32) {
+      throw std::invalid_argument(std::string(who) + ": null f32 pointer");
+    }
+  }
+  int launches = 0;
+  int off = 0;
+  while (off < n) {
+    MxWorkSegArray da{};
+    unsigned long long total = 0;
+    bool vec = true;  // per launch: every segment of it moves as float4
+    while (off < n && da.n < kMaxBatch) {
+      const MxWorkSeg& sg = segs_host[off++];
+      if (sg.n == 0) continue;  // keeps prefix strictly increasing
+      da.d[da.n] = sg;
+      da.prefix[da.n] = total;
+      total += mx::MxSuperblocks(sg.n);
+      vec = vec && Aligned16(sg.f32);
+      ++da.n;
+    }
+    da.prefix[da.n] = total;
+    if (total == 0) continue;
+    // tiles as in LaunchBatchedMx
+    size_t spb = kBlockSupers;
+    if (tile_cap > 0) {
+      spb = (total + tile_cap - 1) / tile_cap;
+      spb = ((spb + kBlockSupers - 1) / kBlockSupers) * kBlockSupers;
+    }
+    unsigned grid = static_cast<unsigned>((total + spb - 1) / spb);
+    if (kQuant) {
+      if (vec) {
+        hipLaunchKernelGGL(batched_mx_quantize_kernel<true>, dim3(grid), dim3(kBlock), 0, s, da,
+                           spb);
+      } else {
+        hipLaunchKernelGGL(batched_mx_quantize_kernel<false>, dim3(grid), dim3(kBlock), 0, s, da,
+                           spb);
+      }
+    } else {
+      if (vec) {
+        hipLaunchKernelGGL(batched_mx_dequantize_kernel<true>, dim3(grid), dim3(kBlock), 0, s, da,
+                           alpha, spb);
+      } else {
+        hipLaunchKernelGGL(batched_mx_dequantize_kernel<false>, dim3(grid), dim3(kBlock), 0, s,
+                           da, alpha, spb);
+      }
+    }
+    ++launches;
+  }
+  return launches;
+}
+
 }  // namespace
 
 void MxQuantize(const float* src, size_t n, void* packed, hipStream_t s, int grid_cap) {
@@ -425,6 +555,15 @@ int BatchedMxAccumulate(const MxSeg* segs_host, int n, bool assign, hipStream_t 
 
 int BatchedMxFinish(const MxSeg* segs_host, int n, hipStream_t s, int tile_cap) {
   return LaunchBatchedMx<2>("BatchedMxFinish", segs_host, n, s, tile_cap);
+}
+
+int BatchedMxQuantize(const MxWorkSeg* segs_host, int n, hipStream_t s, int tile_cap) {
+  return LaunchBatchedMxWork<true>("BatchedMxQuantize", segs_host, n, 1.0f, s, tile_cap);
+}
+
+int BatchedMxDequantize(const MxWorkSeg* segs_host, int n, float alpha, hipStream_t s,
+                        int tile_cap) {
+  return LaunchBatchedMxWork<false>("BatchedMxDequantize", segs_host, n, alpha, s, tile_cap);
 }
 
 }  // namespace kern

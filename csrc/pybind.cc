@@ -1036,6 +1036,36 @@ PYBIND11_MODULE(_core, m) {
           return launches;
         },
         py::arg("segs"), py::arg("tile_cap") = 0);
+  // worker side, batched (f32, packed, n) segments. Returns the number of
+  // launches; 0 (an empty list, or empty segments only) without touching
+  // the GPU at all.
+  using MxWorkSegT = std::tuple<uintptr_t, uintptr_t, size_t>;
+  auto mx_work_segs = [](const std::vector<MxWorkSegT>& segs) {
+    std::vector<kern::MxWorkSeg> v;
+    for (auto& t : segs) {
+      v.push_back(kern::MxWorkSeg{reinterpret_cast<float*>(std::get<0>(t)),
+                                  reinterpret_cast<void*>(std::get<1>(t)), std::get<2>(t)});
+    }
+    return v;
+  };
+  m.def("k_batched_mx_quantize",
+        [mx_work_segs](const std::vector<MxWorkSegT>& segs, int tile_cap) {
+          auto v = mx_work_segs(segs);
+          int launches = kern::BatchedMxQuantize(v.data(), static_cast<int>(v.size()), nullptr,
+                                                 tile_cap);
+          if (launches) gpu::DeviceSync(-1);
+          return launches;
+        },
+        py::arg("segs"), py::arg("tile_cap") = 0);
+  m.def("k_batched_mx_dequantize",
+        [mx_work_segs](const std::vector<MxWorkSegT>& segs, float alpha, int tile_cap) {
+          auto v = mx_work_segs(segs);
+          int launches = kern::BatchedMxDequantize(v.data(), static_cast<int>(v.size()), alpha,
+                                                   nullptr, tile_cap);
+          if (launches) gpu::DeviceSync(-1);
+          return launches;
+        },
+        py::arg("segs"), py::arg("alpha") = 1.0f, py::arg("tile_cap") = 0);
   m.def("k_sparse_gather_f32",
         [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
            int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {

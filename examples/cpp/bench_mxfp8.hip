@@ -7,18 +7,22 @@
 // Cases: one key of 1, 4 and 64 MiB of fp32, and the ResNet-50 gradient
 // bucket list (4 MiB partitions, ps_lite_amd/models/resnet50_buckets.py)
 // in one call. Per case it times
-//   quantize    fp32 -> packed            (reads 4 B, writes 1.03 B per element)
-//   dequantize  packed -> fp32            (reads 1.03, writes 4)
-//   accumulate  acc += D(packed)          (reads 5.03, writes 4)
-//   finish      out = Q(acc + D(packed))  (reads 5.03, writes 1.03)
+//   quantize      fp32 -> packed            (reads 4 B, writes 1.03 B per element)
+//   quantize-b    the same, batched
+//   dequantize    packed -> fp32            (reads 1.03, writes 4)
+//   dequantize-b  the same, batched
+//   accumulate    acc += D(packed)          (reads 5.03, writes 4)
+//   finish        out = Q(acc + D(packed))  (reads 5.03, writes 1.03)
 // and kern::DenseAssign moving the same read + write byte total, every
 // launch between its own pair of HIP events, over 6 or more buffer sets
 // (1.5 GiB or more) in rotation, so that a timed launch finds nothing of its
-// buffers in the 256 MiB Infinity Cache. Accumulate and
-// finish take the bucket list as one batched call (one launch per 64
-// segments); quantize and dequantize have no batched form and run once per
-// bucket, timed as one sequence. Output: GB/s of each kernel's own traffic
-// and its ratio to the copy.
+// buffers in the 256 MiB Infinity Cache. Accumulate, finish and the -b rows
+// take the bucket list as one batched call (one launch per 64 segments);
+// the quantize and dequantize rows run the single kernels once per bucket,
+// timed as one sequence, for comparison. Before timing, the batched
+// quantize and dequantize of set 0 are compared byte for byte with the
+// single kernels' output, every segment. Output: GB/s of each kernel's own
+// traffic and its ratio to the copy.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +47,7 @@
 namespace {
 
 using xps::kern::MxSeg;
+using xps::kern::MxWorkSeg;
 namespace mx = xps::mx;
 
 // finite values with block maxima spread over ~2^16, some exact zeros
@@ -107,6 +112,8 @@ struct BufSet {
   std::vector<MxSeg> segs;     // acc, packed, out per segment
   std::vector<float*> src;     // fp32 source per segment
   std::vector<float*> dq_dst;  // dequantize target per segment (the acc slab)
+  std::vector<MxWorkSeg> qsegs;   // batched quantize: src -> out
+  std::vector<MxWorkSeg> dqsegs;  // batched dequantize: packed -> dq_dst
 };
 
 struct Case {
@@ -142,7 +149,7 @@ int main(int argc, char** argv) {
   CHECK(hipEventCreate(&e1));
   printf("# %d rounds per kernel, median launch time; GB/s = the kernel's own read + write bytes\n",
          rounds);
-  printf("%-14s %-11s %10s %10s %10s %8s\n", "case", "kernel", "us", "GB/s", "copy GB/s", "ratio");
+  printf("%-14s %-12s %10s %10s %10s %8s\n", "case", "kernel", "us", "GB/s", "copy GB/s", "ratio");
 
   for (const Case& c : cases) {
     size_t f32_bytes = 0, packed_bytes = 0;
@@ -181,6 +188,8 @@ int main(int argc, char** argv) {
         b.dq_dst.push_back(acc);
         b.segs.push_back(MxSeg{acc, b.packed + packed_off[i], b.out + packed_off[i],
                                mx::MxPackedBytes(c.elems[i])});
+        b.qsegs.push_back(MxWorkSeg{src, b.out + packed_off[i], c.elems[i]});
+        b.dqsegs.push_back(MxWorkSeg{acc, b.packed + packed_off[i], c.elems[i]});
         xps::kern::MxQuantize(src, c.elems[i], b.packed + packed_off[i], nullptr);
       }
       int nseg = static_cast<int>(b.segs.size());
@@ -209,6 +218,43 @@ int main(int argc, char** argv) {
       }
     }
 
+    // the batched worker-side pair against the single kernels on set 0:
+    // every byte of every segment's packed form, then of the fp32 slab
+    // (0xFF-filled first, so floats past a segment's n count too)
+    {
+      BufSet& b = sets[0];
+      int nseg = static_cast<int>(b.segs.size());
+      std::vector<uint8_t> one(packed_bytes), many(packed_bytes);
+      CHECK(hipMemset(b.out, 0xFF, packed_bytes));
+      xps::kern::BatchedMxQuantize(b.qsegs.data(), nseg, nullptr);
+      CHECK(hipMemcpy(one.data(), b.packed, packed_bytes, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(many.data(), b.out, packed_bytes, hipMemcpyDeviceToHost));
+      size_t bad = 0;
+      for (size_t i = 0; i < packed_bytes; ++i) bad += one[i] != many[i];
+      if (bad) {
+        fprintf(stderr, "%s: batched quantize differs from the single kernel in %zu bytes\n",
+                c.name.c_str(), bad);
+        return 1;
+      }
+      std::vector<uint8_t> fone(f32_bytes), fmany(f32_bytes);
+      CHECK(hipMemset(b.acc, 0xFF, f32_bytes));
+      for (int i = 0; i < nseg; ++i) {
+        xps::kern::MxDequantize(b.segs[i].in, c.elems[i], b.dq_dst[i], 1.0f, nullptr);
+      }
+      CHECK(hipMemcpy(fone.data(), b.acc, f32_bytes, hipMemcpyDeviceToHost));
+      CHECK(hipMemset(b.acc, 0xFF, f32_bytes));
+      xps::kern::BatchedMxDequantize(b.dqsegs.data(), nseg, 1.0f, nullptr);
+      CHECK(hipMemcpy(fmany.data(), b.acc, f32_bytes, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < f32_bytes; ++i) bad += fone[i] != fmany[i];
+      if (bad) {
+        fprintf(stderr, "%s: batched dequantize differs from the single kernel in %zu bytes\n",
+                c.name.c_str(), bad);
+        return 1;
+      }
+      xps::kern::BatchedMxAccumulate(b.segs.data(), nseg, /*assign=*/true, nullptr);
+      CHECK(hipDeviceSynchronize());
+    }
+
     double n_total = 0;
     for (size_t n : c.elems) {
       n_total += static_cast<double>(mx::MxSuperblocks(n) * mx::kSuperElems);
@@ -218,8 +264,10 @@ int main(int argc, char** argv) {
       const char* name;
       double bytes;  // read + write
       int id;
-    } kerns[4] = {{"quantize", n_total * (4 + pk), 0},
+    } kerns[6] = {{"quantize", n_total * (4 + pk), 0},
+                  {"quantize-b", n_total * (4 + pk), 4},
                   {"dequantize", n_total * (4 + pk), 1},
+                  {"dequantize-b", n_total * (4 + pk), 5},
                   {"accumulate", n_total * (8 + pk), 2},
                   {"finish", n_total * (4 + 2 * pk), 3}};
     for (const Kern& k : kerns) {
@@ -245,6 +293,12 @@ int main(int argc, char** argv) {
             break;
           case 2:
             xps::kern::BatchedMxAccumulate(b.segs.data(), nseg, /*assign=*/false, nullptr);
+            break;
+          case 4:
+            xps::kern::BatchedMxQuantize(b.qsegs.data(), nseg, nullptr);
+            break;
+          case 5:
+            xps::kern::BatchedMxDequantize(b.dqsegs.data(), nseg, 1.0f, nullptr);
             break;
           default:
             xps::kern::BatchedMxFinish(b.segs.data(), nseg, nullptr);
@@ -272,7 +326,7 @@ int main(int argc, char** argv) {
       double med = Median(&us), med_copy = Median(&us_copy);
       double gbs = k.bytes / (med * 1e-6) / 1e9;
       double gbs_copy = 2.0 * copy_bytes / (med_copy * 1e-6) / 1e9;
-      printf("%-14s %-11s %10.2f %10.1f %10.1f %8.2f\n", c.name.c_str(), k.name, med, gbs, gbs_copy,
+      printf("%-14s %-12s %10.2f %10.1f %10.1f %8.2f\n", c.name.c_str(), k.name, med, gbs, gbs_copy,
              gbs / gbs_copy);
       fflush(stdout);
     }

@@ -21,12 +21,18 @@ import numpy as np
 
 class PSGradSync:
     def __init__(self, ps, worker, params, num_workers, device=-1,
-                 partition_bytes=4 << 20, mode=None, key_base=1 << 20, compress=None):
+                 partition_bytes=4 << 20, mode=None, key_base=1 << 20, compress=None,
+                 mx_batched=True):
         if compress not in (None, "mxfp8"):
             raise ValueError(f"unknown compress={compress!r} (None or 'mxfp8')")
         if compress and (device < 0 or (mode or "reduce") != "reduce"):
             raise ValueError("compress='mxfp8' needs a GPU (device >= 0) and reduce mode")
         self.compress = compress
+        # compress="mxfp8" only: quantize and dequantize all buckets in one
+        # launch per 64 (True) or one launch per bucket (False, the A/B)
+        self.mx_batched = bool(mx_batched)
+        # worker-side quantize and dequantize launches so far
+        self.mx_launches = 0
         self.ps = ps
         self.worker = worker
         self.params = list(params)
@@ -87,11 +93,19 @@ class PSGradSync:
         The servers run set_gpu_dense_handle(mode="reduce", dtype="mxfp8")."""
         core = self.ps._core
         keys = self._keys()
+        nb = len(self.buckets)
+        if self.mx_batched:
+            # grads may be reallocated between steps: pointers are read now
+            gptrs = [self._grad_view(b).data_ptr() for b in range(nb)]
+            self.mx_launches += core.k_batched_mx_quantize(
+                [(gptrs[b], self.bufs[b].ptr, self.buckets[b][2]) for b in range(nb)])
         tss = []
         for b, k in enumerate(keys):
             elems = self.buckets[b][2]
             nbytes = core.mxfp8_packed_nbytes(elems)
-            core.k_mx_quantize(self._grad_view(b).data_ptr(), elems, self.bufs[b].ptr)
+            if not self.mx_batched:
+                core.k_mx_quantize(self._grad_view(b).data_ptr(), elems, self.bufs[b].ptr)
+                self.mx_launches += 1
             ka = np.array([k], dtype=np.uint64)
             lens = np.array([nbytes // 4], dtype=np.int32)
             tss.append(self.worker.zpush_ptr(ka, self.bufs[b].ptr, nbytes, self.device, lens,
@@ -101,9 +115,15 @@ class PSGradSync:
         for ts in tss:
             self.worker.wait(ts)
         inv = 1.0 / self.num_workers
-        for b in range(len(self.buckets)):
-            elems = self.buckets[b][2]
-            core.k_mx_dequantize(self.pull_bufs[b].ptr, elems, self._grad_view(b).data_ptr(), inv)
+        if self.mx_batched:
+            self.mx_launches += core.k_batched_mx_dequantize(
+                [(gptrs[b], self.pull_bufs[b].ptr, self.buckets[b][2]) for b in range(nb)], inv)
+        else:
+            for b in range(nb):
+                elems = self.buckets[b][2]
+                core.k_mx_dequantize(self.pull_bufs[b].ptr, elems, self._grad_view(b).data_ptr(),
+                                     inv)
+                self.mx_launches += 1
         self.step_count += 1
 
     def allreduce(self):
