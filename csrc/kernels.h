@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coalesce_admit.h"
+#include "kernel_util.h"
 
 namespace xps {
 namespace kern {
@@ -69,7 +70,6 @@ void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows
 // Batched segmented copy/accumulate: one launch serving up to
 // kMaxBatch (dst, src, nbytes) segments — the device-side slicing/merge
 // of SURVEY.md §2.6 item 3, used for multi-key messages.
-static const int kMaxBatch = 64;
 struct CopyDesc {
   void* dst;
   const void* src;
@@ -80,10 +80,7 @@ struct CopyDesc {
 // through the per-segment launchers, which take any skew.
 inline bool BatchAligned(const CopyDesc* descs, size_t n) {
   for (size_t i = 0; i < n; ++i) {
-    if ((reinterpret_cast<uintptr_t>(descs[i].dst) | reinterpret_cast<uintptr_t>(descs[i].src) |
-         descs[i].nbytes) & 15u) {
-      return false;
-    }
+    if (!Aligned16(descs[i].dst, descs[i].src) || descs[i].nbytes % 16) return false;
   }
   return true;
 }

@@ -20,9 +20,9 @@
 // instruction's overflow mode never matters.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "kernels.h"
 #include "mxfp8.h"
@@ -33,7 +33,6 @@ namespace kern {
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kLaneElems = 16;                    // elements owned by one lane
 constexpr int kSuperLanes = 32;                   // lanes per superblock
 constexpr int kBlockSupers = kBlock / kSuperLanes;  // superblocks per block stride
@@ -180,13 +179,13 @@ __device__ inline void StorePacked(uint8_t* __restrict__ packed, size_t u, uint4
   if (slot < 4) reinterpret_cast<uint32_t*>(sb)[slot] = word;
 }
 
-template <bool kVec>
-__global__ void __launch_bounds__(kBlock)
-    mx_quantize_kernel(const float* __restrict__ src, size_t n, uint8_t* __restrict__ packed,
-                       size_t units) {
-  size_t u = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
-  size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
-  for (; u < units; u += stride) {
+// packed = Q(src[0, n)) for the 16-element units u, u + stride, ... below
+// end. Whole superblocks of lanes arrive together (StorePacked); a lane
+// past n loads zeros.
+template <bool kVec, class Stride>
+__device__ __forceinline__ void QuantUnits(const float* src, size_t n, uint8_t* packed, size_t u,
+                                           size_t end, Stride stride) {
+  for (; u < end; u += stride) {
     float v[kLaneElems];
     Load16Bounded<kVec>(src, u * kLaneElems, n, v);
     uint32_t byte;
@@ -195,21 +194,29 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+template <bool kVec>
+__global__ void __launch_bounds__(kBlock)
+    mx_quantize_kernel(const float* __restrict__ src, size_t n, uint8_t* __restrict__ packed,
+                       size_t units) {
+  size_t u = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
+  QuantUnits<kVec>(src, n, packed, u, units, stride);
+}
+
 constexpr int kQuadSteps = 4;  // independent quads in flight per lane
 
 __device__ inline float4 Scale4(float4 v, float alpha) {
   return float4{v.x * alpha, v.y * alpha, v.z * alpha, v.w * alpha};
 }
 
-template <bool kVec>
-__global__ void __launch_bounds__(kBlock)
-    mx_dequantize_kernel(const uint8_t* __restrict__ packed, size_t n, float* __restrict__ dst,
-                         float alpha, size_t quads) {
-  size_t q = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
-  size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
-  // whole quads, kQuadSteps of them per trip: all loads ahead of the stores
-  size_t whole = n / kQuadElems;
-  for (; q + (kQuadSteps - 1) * stride < whole; q += kQuadSteps * stride) {
+// dst[0, n) = D(packed) * alpha for the quads q, q + stride, ... below end:
+// kQuadSteps quads per trip while they lie below whole_end <= n / 4, all of
+// a lane's loads ahead of its stores, then quad by quad.
+template <bool kVec, class Stride>
+__device__ __forceinline__ void DequantQuads(const uint8_t* packed, size_t n, float* dst,
+                                             float alpha, size_t q, size_t whole_end, size_t end,
+                                             Stride stride) {
+  for (; q + (kQuadSteps - 1) * stride < whole_end; q += kQuadSteps * stride) {
     float4 v[kQuadSteps];
 #pragma unroll
     for (int j = 0; j < kQuadSteps; ++j) v[j] = Dequant4(packed, q + j * stride);
@@ -218,7 +225,7 @@ __global__ void __launch_bounds__(kBlock)
       Store4<kVec>(dst + (q + j * stride) * kQuadElems, Scale4(v[j], alpha));
     }
   }
-  for (; q < quads; q += stride) {
+  for (; q < end; q += stride) {
     float4 v = Scale4(Dequant4(packed, q), alpha);
     size_t base = q * kQuadElems;
     if (base + kQuadElems <= n) {
@@ -231,11 +238,14 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-struct MxSegArray {
-  MxSeg d[kMaxBatch];
-  unsigned long long prefix[kMaxBatch + 1];  // superblock offsets, prefix[n] = total
-  int n;
-};
+template <bool kVec>
+__global__ void __launch_bounds__(kBlock)
+    mx_dequantize_kernel(const uint8_t* __restrict__ packed, size_t n, float* __restrict__ dst,
+                         float alpha, size_t quads) {
+  size_t q = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
+  DequantQuads<kVec>(packed, n, dst, alpha, q, n / kQuadElems, quads, stride);
+}
 
 // Server side, up to kMaxBatch segments concatenated in superblock space.
 // Each block owns one contiguous tile of supers_per_block superblocks and
@@ -246,7 +256,7 @@ struct MxSegArray {
 // kVec: every segment's acc is 16 B-aligned
 template <int kOp, bool kVec>
 __global__ void __launch_bounds__(kBlock)
-    batched_mx_kernel(MxSegArray da, size_t supers_per_block) {
+    batched_mx_kernel(SegTable<MxSeg> da, size_t supers_per_block) {
   TileRunIter it = TileRunsBegin(da.prefix, da.n, supers_per_block, blockIdx.x);
   TileRun run;
   while (TileRunsNext(da.prefix, &it, &run)) {
@@ -307,15 +317,6 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-inline int GridFor(size_t units, int grid_cap) {
-  size_t g = (units + kBlock - 1) / kBlock;
-  if (g > 8192) g = 8192;
-  if (grid_cap > 0 && g > static_cast<size_t>(grid_cap)) g = grid_cap;
-  return static_cast<int>(g ? g : 1);
-}
-
-inline bool Aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 void CheckPacked(const char* who, const void* packed, size_t nbytes) {
   if (!Aligned16(packed)) {
     throw std::invalid_argument(std::string(who) + ": packed pointer is not 16 B-aligned");
@@ -324,6 +325,31 @@ void CheckPacked(const char* who, const void* packed, size_t nbytes) {
     throw std::invalid_argument(std::string(who) + ": packed length " + std::to_string(nbytes) +
                                 " is not a multiple of 528");
   }
+}
+
+// kVec from a run-time test: launch(std::true_type or std::false_type)
+template <class Launch>
+void WithVec(bool vec, Launch launch) {
+  if (vec) {
+    launch(std::true_type{});
+  } else {
+    launch(std::false_type{});
+  }
+}
+
+// a launch moves fp32 as float4 when every segment of its table can
+template <class Seg>
+bool TableAligned16(const SegTable<Seg>& da, float* Seg::*f32) {
+  for (int i = 0; i < da.n; ++i) {
+    if (!Aligned16(da.d[i].*f32)) return false;
+  }
+  return true;
+}
+
+// one stride of the block (8 superblocks, 16 KiB of fp32) per tile; a
+// tile_cap grows the tile, in whole strides, until the grid fits it
+size_t MxTile(size_t total, int tile_cap) {
+  return TileChunks(total, kBlockSupers, kAnyBlocks, 0, tile_cap);
 }
 
 template <int kOp>
@@ -335,46 +361,16 @@ int LaunchBatchedMx(const char* who, const MxSeg* segs_host, int n, hipStream_t 
       throw std::invalid_argument(std::string(who) + ": null accumulator");
     }
   }
-  bool vec = true;
-  for (int i = 0; i < n; ++i) vec = vec && Aligned16(segs_host[i].acc);
-  int launches = 0;
-  int off = 0;
-  while (off < n) {
-    MxSegArray da{};
-    unsigned long long total = 0;
-    while (off < n && da.n < kMaxBatch) {
-      const MxSeg& sg = segs_host[off++];
-      if (sg.nbytes == 0) continue;  // keeps prefix strictly increasing
-      da.d[da.n] = sg;
-      da.prefix[da.n] = total;
-      total += sg.nbytes / mx::kSuperBytes;
-      ++da.n;
-    }
-    da.prefix[da.n] = total;
-    if (total == 0) continue;
-    // one stride of the block (8 superblocks, 16 KiB of fp32) per tile; a
-    // tile_cap grows the tile, in whole strides, until the grid fits it
-    size_t spb = kBlockSupers;
-    if (tile_cap > 0) {
-      spb = (total + tile_cap - 1) / tile_cap;
-      spb = ((spb + kBlockSupers - 1) / kBlockSupers) * kBlockSupers;
-    }
-    unsigned grid = static_cast<unsigned>((total + spb - 1) / spb);
-    if (vec) {
-      hipLaunchKernelGGL((batched_mx_kernel<kOp, true>), dim3(grid), dim3(kBlock), 0, s, da, spb);
-    } else {
-      hipLaunchKernelGGL((batched_mx_kernel<kOp, false>), dim3(grid), dim3(kBlock), 0, s, da, spb);
-    }
-    ++launches;
-  }
-  return launches;
+  return ForEachTable(
+      segs_host, n, [](const MxSeg& sg) { return sg.nbytes / mx::kSuperBytes; },
+      [&](const SegTable<MxSeg>& da, size_t total) {
+        size_t spb = MxTile(total, tile_cap);
+        WithVec(TableAligned16(da, &MxSeg::acc), [&](auto vec) {
+          hipLaunchKernelGGL((batched_mx_kernel<kOp, decltype(vec)::value>),
+                             dim3(TileGrid(total, spb)), dim3(kBlock), 0, s, da, spb);
+        });
+      });
 }
-
-struct MxWorkSegArray {
-  MxWorkSeg d[kMaxBatch];
-  unsigned long long prefix[kMaxBatch + 1];  // superblock offsets, prefix[n] = total
-  int n;
-};
 
 // Worker side, up to kMaxBatch segments concatenated in superblock space
 // and tiled like batched_mx_kernel: block-uniform table reads, uniform base
@@ -383,64 +379,33 @@ struct MxWorkSegArray {
 // kVec: every segment's f32 is 16 B-aligned
 template <bool kVec>
 __global__ void __launch_bounds__(kBlock)
-    batched_mx_quantize_kernel(MxWorkSegArray da, size_t supers_per_block) {
+    batched_mx_quantize_kernel(SegTable<MxWorkSeg> da, size_t supers_per_block) {
   TileRunIter it = TileRunsBegin(da.prefix, da.n, supers_per_block, blockIdx.x);
   TileRun run;
   while (TileRunsNext(da.prefix, &it, &run)) {
-    const float* __restrict__ src = da.d[run.seg].f32;
-    uint8_t* __restrict__ packed = static_cast<uint8_t*>(da.d[run.seg].packed);
-    size_t n = da.d[run.seg].n;
-    // whole superblocks of lanes (StorePacked); a lane past n loads zeros
-    size_t end = run.hi * kSuperLanes;
-    for (size_t u = run.lo * kSuperLanes + threadIdx.x; u < end; u += kBlock) {
-      float v[kLaneElems];
-      Load16Bounded<kVec>(src, u * kLaneElems, n, v);
-      uint32_t byte;
-      uint4 codes = Quant16(v, &byte);
-      StorePacked(packed, u, codes, byte);
-    }
+    QuantUnits<kVec>(da.d[run.seg].f32, da.d[run.seg].n,
+                     static_cast<uint8_t*>(da.d[run.seg].packed),
+                     run.lo * kSuperLanes + threadIdx.x, run.hi * kSuperLanes, kBlock);
   }
 }
 
 template <bool kVec>
 __global__ void __launch_bounds__(kBlock)
-    batched_mx_dequantize_kernel(MxWorkSegArray da, float alpha, size_t supers_per_block) {
+    batched_mx_dequantize_kernel(SegTable<MxWorkSeg> da, float alpha, size_t supers_per_block) {
   TileRunIter it = TileRunsBegin(da.prefix, da.n, supers_per_block, blockIdx.x);
   TileRun run;
   while (TileRunsNext(da.prefix, &it, &run)) {
-    float* __restrict__ dst = da.d[run.seg].f32;
-    const uint8_t* __restrict__ packed = static_cast<const uint8_t*>(da.d[run.seg].packed);
     size_t n = da.d[run.seg].n;
     // the run's quads end with the segment's elements, not with its last
     // superblock
     size_t run_end = run.hi * kSuperQuads;
     size_t quads = (n + kQuadElems - 1) / kQuadElems;
     size_t whole = n / kQuadElems;
-    size_t end = run_end < quads ? run_end : quads;
-    size_t whole_end = run_end < whole ? run_end : whole;
-    size_t q = run.lo * kSuperQuads + threadIdx.x;
-    // a whole tile is kQuadSteps strides of the block: all of a lane's
-    // loads go out ahead of its stores
-    for (; q + (kQuadSteps - 1) * kBlock < whole_end; q += kQuadSteps * kBlock) {
-      float4 v[kQuadSteps];
-#pragma unroll
-      for (int j = 0; j < kQuadSteps; ++j) v[j] = Dequant4(packed, q + j * kBlock);
-#pragma unroll
-      for (int j = 0; j < kQuadSteps; ++j) {
-        Store4<kVec>(dst + (q + j * kBlock) * kQuadElems, Scale4(v[j], alpha));
-      }
-    }
-    for (; q < end; q += kBlock) {
-      float4 v = Scale4(Dequant4(packed, q), alpha);
-      size_t base = q * kQuadElems;
-      if (base + kQuadElems <= n) {
-        Store4<kVec>(dst + base, v);
-      } else {  // the quad that holds element n - 1: nothing is written past n
-        if (base < n) dst[base] = v.x;
-        if (base + 1 < n) dst[base + 1] = v.y;
-        if (base + 2 < n) dst[base + 2] = v.z;
-      }
-    }
+    // a whole tile is kQuadSteps strides of the block
+    DequantQuads<kVec>(static_cast<const uint8_t*>(da.d[run.seg].packed), n, da.d[run.seg].f32,
+                       alpha, run.lo * kSuperQuads + threadIdx.x,
+                       run_end < whole ? run_end : whole, run_end < quads ? run_end : quads,
+                       kBlock);
   }
 }
 
@@ -454,50 +419,21 @@ int LaunchBatchedMxWork(const char* who, const MxWorkSeg* segs_host, int n, floa
       throw std::invalid_argument(std::string(who) + ": null f32 pointer");
     }
   }
-  int launches = 0;
-  int off = 0;
-  while (off < n) {
-    MxWorkSegArray da{};
-    unsigned long long total = 0;
-    bool vec = true;  // per launch: every segment of it moves as float4
-    while (off < n && da.n < kMaxBatch) {
-      const MxWorkSeg& sg = segs_host[off++];
-      if (sg.n == 0) continue;  // keeps prefix strictly increasing
-      da.d[da.n] = sg;
-      da.prefix[da.n] = total;
-      total += mx::MxSuperblocks(sg.n);
-      vec = vec && Aligned16(sg.f32);
-      ++da.n;
-    }
-    da.prefix[da.n] = total;
-    if (total == 0) continue;
-    // tiles as in LaunchBatchedMx
-    size_t spb = kBlockSupers;
-    if (tile_cap > 0) {
-      spb = (total + tile_cap - 1) / tile_cap;
-      spb = ((spb + kBlockSupers - 1) / kBlockSupers) * kBlockSupers;
-    }
-    unsigned grid = static_cast<unsigned>((total + spb - 1) / spb);
-    if (kQuant) {
-      if (vec) {
-        hipLaunchKernelGGL(batched_mx_quantize_kernel<true>, dim3(grid), dim3(kBlock), 0, s, da,
-                           spb);
-      } else {
-        hipLaunchKernelGGL(batched_mx_quantize_kernel<false>, dim3(grid), dim3(kBlock), 0, s, da,
-                           spb);
-      }
-    } else {
-      if (vec) {
-        hipLaunchKernelGGL(batched_mx_dequantize_kernel<true>, dim3(grid), dim3(kBlock), 0, s, da,
-                           alpha, spb);
-      } else {
-        hipLaunchKernelGGL(batched_mx_dequantize_kernel<false>, dim3(grid), dim3(kBlock), 0, s,
-                           da, alpha, spb);
-      }
-    }
-    ++launches;
-  }
-  return launches;
+  return ForEachTable(
+      segs_host, n, [](const MxWorkSeg& sg) { return mx::MxSuperblocks(sg.n); },
+      [&](const SegTable<MxWorkSeg>& da, size_t total) {
+        size_t spb = MxTile(total, tile_cap);
+        dim3 grid(TileGrid(total, spb));
+        WithVec(TableAligned16(da, &MxWorkSeg::f32), [&](auto vec) {
+          constexpr bool kVec = decltype(vec)::value;
+          if constexpr (kQuant) {
+            hipLaunchKernelGGL(batched_mx_quantize_kernel<kVec>, grid, dim3(kBlock), 0, s, da, spb);
+          } else {
+            hipLaunchKernelGGL(batched_mx_dequantize_kernel<kVec>, grid, dim3(kBlock), 0, s, da,
+                               alpha, spb);
+          }
+        });
+      });
 }
 
 }  // namespace
@@ -506,13 +442,12 @@ void MxQuantize(const float* src, size_t n, void* packed, hipStream_t s, int gri
   CheckPacked("MxQuantize", packed, 0);
   if (n == 0) return;
   size_t units = mx::MxSuperblocks(n) * kSuperLanes;
-  dim3 grid(GridFor(units, grid_cap));
+  dim3 grid(GridFor(units, 8192, grid_cap));
   uint8_t* out = static_cast<uint8_t*>(packed);
-  if (Aligned16(src)) {
-    hipLaunchKernelGGL(mx_quantize_kernel<true>, grid, dim3(kBlock), 0, s, src, n, out, units);
-  } else {
-    hipLaunchKernelGGL(mx_quantize_kernel<false>, grid, dim3(kBlock), 0, s, src, n, out, units);
-  }
+  WithVec(Aligned16(src), [&](auto vec) {
+    hipLaunchKernelGGL(mx_quantize_kernel<decltype(vec)::value>, grid, dim3(kBlock), 0, s, src, n,
+                       out, units);
+  });
 }
 
 void MxDequantize(const void* packed, size_t n, float* dst, float alpha, hipStream_t s,
@@ -521,15 +456,12 @@ void MxDequantize(const void* packed, size_t n, float* dst, float alpha, hipStre
   if (n == 0) return;
   size_t quads = (n + kQuadElems - 1) / kQuadElems;
   size_t lanes = (quads + kQuadSteps - 1) / kQuadSteps;
-  dim3 grid(GridFor(lanes, grid_cap));
+  dim3 grid(GridFor(lanes, 8192, grid_cap));
   const uint8_t* in = static_cast<const uint8_t*>(packed);
-  if (Aligned16(dst)) {
-    hipLaunchKernelGGL(mx_dequantize_kernel<true>, grid, dim3(kBlock), 0, s, in, n, dst, alpha,
-                       quads);
-  } else {
-    hipLaunchKernelGGL(mx_dequantize_kernel<false>, grid, dim3(kBlock), 0, s, in, n, dst, alpha,
-                       quads);
-  }
+  WithVec(Aligned16(dst), [&](auto vec) {
+    hipLaunchKernelGGL(mx_dequantize_kernel<decltype(vec)::value>, grid, dim3(kBlock), 0, s, in, n,
+                       dst, alpha, quads);
+  });
 }
 
 void MxAccumulate(float* acc, const void* packed, size_t nbytes, bool assign, hipStream_t s,

@@ -650,6 +650,17 @@ PYBIND11_MODULE(_core, m) {
           return out;
         },
         py::arg("chunk_counts"), py::arg("chunks_per_block"), py::arg("block_index"));
+  // the batched launchers' tile rule (tile_runs.h, the same code they run)
+  m.def("tile_size",
+        [](unsigned long long total, unsigned long long stride, unsigned long long want_blocks,
+           unsigned long long max_tile, int tile_cap) {
+          if (total == 0 || stride == 0 || want_blocks == 0) {
+            throw std::invalid_argument("tile_size: total, stride and want_blocks must be > 0");
+          }
+          return kern::TileChunks(total, stride, want_blocks, max_tile, tile_cap);
+        },
+        py::arg("total"), py::arg("stride"), py::arg("want_blocks"), py::arg("max_tile"),
+        py::arg("tile_cap"));
 
   // per-peer plane traffic: {node_id: (tx_bytes, rx_bytes)} — each peer
   // pair rides its own xGMI link, so this is the per-link utilization

@@ -1,8 +1,9 @@
-// Run enumeration of the batched dual-write kernel (kernels.hip): which
-// pieces of which segments does one block's tile of the concatenated
-// 16 B-chunk space cover? Pure arithmetic on block-uniform values, no
-// HIP calls — the kernel runs it on the scalar side, the host runs the
-// very same code in tests/test_tile_runs.py (no GPU needed).
+// Tiling of the batched kernels' concatenated unit space (kernels.hip,
+// mxfp8.hip). Run enumeration: which pieces of which segments does one
+// block's tile cover? Pure arithmetic on block-uniform values, no HIP
+// calls — the kernels run it on the scalar side, the host runs the very
+// same code in tests/test_tile_runs.py (no GPU needed). And the launchers'
+// tile rule, tested there too.
 #pragma once
 
 #include <cstddef>
@@ -82,6 +83,28 @@ XPS_HOST_DEVICE inline bool TileRunsNext(const unsigned long long* prefix, TileR
   it->pos = stop;
   ++it->seg;
   return true;
+}
+
+// Tile size of a batched launch over `total` units: enough tiles for
+// want_blocks blocks (fewer under a tile_cap > 0, the tests' cap on the
+// grid), in whole multiples of `stride`, the units one sweep of the block
+// covers. max_tile > 0 bounds the tile, so that a large launch grows its
+// grid instead; a tile_cap is obeyed as given and lifts that bound.
+constexpr unsigned long long kAnyBlocks = ~0ull;  // want_blocks: one stride per tile
+inline unsigned long long TileChunks(unsigned long long total, unsigned long long stride,
+                                     unsigned long long want_blocks,
+                                     unsigned long long max_tile, int tile_cap) {
+  unsigned long long blocks = want_blocks;
+  if (tile_cap > 0 && static_cast<unsigned long long>(tile_cap) < blocks) blocks = tile_cap;
+  unsigned long long tile = total / blocks + (total % blocks != 0);
+  tile = (tile + stride - 1) / stride * stride;
+  if (tile_cap <= 0 && max_tile > 0 && tile > max_tile) tile = max_tile;
+  return tile;
+}
+
+// blocks that cover `total` units in tiles of `tile`
+inline unsigned TileGrid(unsigned long long total, unsigned long long tile) {
+  return static_cast<unsigned>((total + tile - 1) / tile);
 }
 
 }  // namespace kern

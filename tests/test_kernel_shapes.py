@@ -410,7 +410,7 @@ def _legacy_results():
 
 @pytest.mark.parametrize("cid", _BATCHED_IDS)
 def test_batched_shapes_legacy_kernels_in_child(cid):
-    """The same cases through batched_assign_kernel / batched_sum_kernel_*:
+    """The same cases through batched_legacy_kernel (XPS_BALANCED_BATCH=0):
     one child process for all of them, started by the first case."""
     res = _legacy_results()
     assert res["env"] == "0"

@@ -83,3 +83,53 @@ def test_rejects_empty_segment_and_tile():
         _runs([4, 0, 4], 256, 0)
     with pytest.raises(ValueError):
         _runs([4], 0, 0)
+
+
+# The launchers' tile rule (TileChunks in csrc/tile_runs.h) against the three
+# formulas it replaced, written out: (stride, want_blocks, max_tile) per policy.
+_ANY = 2**64 - 1
+_POLICIES = {
+    "balanced": (256, 8192, 0),
+    "dual_write": (256, 8192, 512),
+    "mxfp8": (8, _ANY, 0),
+}
+_TOTALS = [1, 255, 256, 257, 8192 * 256 - 1, 8192 * 256, 8192 * 256 + 1, 8192 * 512 + 1,
+           2**32 + 5]
+_CAPS = [0, 1, 2, 3, 5, 8192, 10000]
+
+
+def _ceil(a, b):
+    return (a + b - 1) // b
+
+
+def _old_tile(policy, total, cap):
+    if policy == "mxfp8":
+        spb = 8
+        if cap > 0:
+            spb = _ceil(_ceil(total, cap), 8) * 8
+        return spb
+    max_blocks = min(cap, 8192) if cap > 0 else 8192
+    cpb = _ceil(_ceil(total, max_blocks), 256) * 256
+    if policy == "dual_write" and cap <= 0 and cpb > 512:
+        cpb = 512
+    return cpb
+
+
+@pytest.mark.parametrize("policy", sorted(_POLICIES))
+def test_tile_size_matches_the_three_policies(policy):
+    stride, want, max_tile = _POLICIES[policy]
+    for total in _TOTALS:
+        for cap in _CAPS:
+            tile = ps._core.tile_size(total, stride, want, max_tile, cap)
+            assert tile == _old_tile(policy, total, cap), (total, cap)
+            assert tile > 0 and tile % stride == 0, (total, cap)
+            blocks = _ceil(total, tile)
+            assert blocks * tile >= total > (blocks - 1) * tile, (total, cap)
+            if cap > 0:
+                assert blocks <= cap, (total, cap)
+
+
+def test_tile_size_rejects_zero():
+    for args in [(0, 256, 8192, 0, 0), (1, 0, 8192, 0, 0), (1, 256, 0, 0, 0)]:
+        with pytest.raises(ValueError):
+            ps._core.tile_size(*args)
