@@ -46,6 +46,10 @@ build/%.hip.o: %.hip csrc/*.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
+# the optimizer kernels keep fp32 operations unpaired: every multiply, add
+# and divide rounds once, as their error bound counts them
+build/csrc/sparse_opt.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(TARGET): $(OBJS)
 	$(HIPCC) $(LDFLAGS) $(OBJS) -o $@
 
@@ -85,6 +89,15 @@ mxfp8bench: build/csrc/kernels.hip.o build/csrc/mxfp8.hip.o build/bench_mxfp8.o
 	$(HIPCC) $(CPPBENCH_LD) build/bench_mxfp8.o build/csrc/kernels.hip.o \
 	    build/csrc/mxfp8.hip.o -o build/bench_mxfp8
 
+# one-process timing of the fused Adagrad step against scatter-add + gather
+# (links kernels.hip and sparse_opt.hip only): build/bench_sparse_adagrad
+build/bench_sparse_adagrad.o: examples/cpp/bench_sparse_adagrad.hip csrc/*.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_sparse_adagrad.hip -o build/bench_sparse_adagrad.o
+adagradbench: build/csrc/kernels.hip.o build/csrc/sparse_opt.hip.o build/bench_sparse_adagrad.o
+	$(HIPCC) $(CPPBENCH_LD) build/bench_sparse_adagrad.o build/csrc/kernels.hip.o \
+	    build/csrc/sparse_opt.hip.o -o build/bench_sparse_adagrad
+
 # self-contained lint gate (reference parity: tests/lint.py + make lint)
 lint:
 	python3 scripts/lint.py
@@ -94,4 +107,4 @@ lint:
 check: all lint
 	python3 -m pytest tests -q -m "not gpu"
 
-.PHONY: all clean cppbench dualwritebench mxfp8bench lint check
+.PHONY: all clean cppbench dualwritebench mxfp8bench adagradbench lint check

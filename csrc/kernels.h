@@ -66,6 +66,22 @@ void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows
                             const float* src, hipStream_t s, int key_shift = 0,
                             uint64_t row_base = 0, uint64_t table_rows = ~0ull,
                             int grid_cap = 0);
+// Adagrad step on the rows r whose decoded row lies in the table, g = grad[r]
+// (sparse_opt.hip):
+//   rowwise:      state[row]    += sum(g * g) / row_len  (one float per row)
+//   element-wise: state[row][c] += g[c] * g[c]           (the table's shape)
+//   table[row][c] -= lr * g[c] / (sqrt(new state) + eps)
+// With out_or_null set, out[r] receives the new row, or zeros for a row
+// outside the table (what the gather gives); table and state are not
+// touched for such a row. In-range rows of one call must be unique, and
+// table, state, grad and out pairwise disjoint. Rows move as float4 when
+// row_len % 4 == 0 and table, grad, out (and an element-wise state) are
+// 16 B-aligned, else as single floats. lr <= 0 or eps <= 0 is
+// std::invalid_argument and nothing is launched.
+void SparseAdagradF32(float* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                      size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
+                      bool rowwise, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
+                      uint64_t table_rows = ~0ull, int grid_cap = 0);
 
 // Batched segmented copy/accumulate: one launch serving up to
 // kMaxBatch (dst, src, nbytes) segments — the device-side slicing/merge

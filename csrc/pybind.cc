@@ -329,9 +329,30 @@ class PyKVServer {
     });
   }
 
-  void SetGpuSparseHandle(size_t rows, size_t row_len, bool accumulate, int key_shift) {
+  // optimizer: None, "adagrad" or "rowwise_adagrad". Bad arguments raise
+  // ValueError before the handler (and with it the GPU) is touched.
+  void SetGpuSparseHandle(size_t rows, size_t row_len, bool accumulate, int key_shift,
+                          py::object optimizer, float lr, float eps, float init_acc) {
+    SparseOptConfig opt;
+    if (!optimizer.is_none()) {
+      std::string name = py::cast<std::string>(optimizer);
+      if (name == "adagrad") {
+        opt.kind = SparseOpt::kAdagrad;
+      } else if (name == "rowwise_adagrad") {
+        opt.kind = SparseOpt::kRowwiseAdagrad;
+      } else {
+        throw py::value_error("optimizer must be None, \"adagrad\" or \"rowwise_adagrad\" (got \"" +
+                              name + "\")");
+      }
+    }
+    if (!(lr > 0.f)) throw py::value_error("lr must be positive");
+    if (!(eps > 0.f)) throw py::value_error("eps must be positive");
+    if (!(init_acc >= 0.f)) throw py::value_error("init_acc must not be negative");
+    opt.lr = lr;
+    opt.eps = eps;
+    opt.init_acc = init_acc;
     auto h = std::make_shared<GpuSparseHandler>(s_.postoffice(), rows, row_len, accumulate,
-                                                key_shift);
+                                                key_shift, opt);
     sparse_ = h;
     s_.set_request_handle([h](const KVMeta& m, const KVPairs<float>& kvs, KVServer<float>* srv) {
       (*h)(m, kvs, srv);
@@ -339,6 +360,12 @@ class PyKVServer {
   }
 
   uintptr_t SparseTablePtr() const { return sparse_ ? sparse_->table_ptr() : 0; }
+  uintptr_t SparseStatePtr() const { return sparse_ ? sparse_->state_ptr() : 0; }
+  void SetSparseLr(float lr) {
+    if (!(lr > 0.f)) throw py::value_error("lr must be positive");
+    XPS_CHECK(sparse_) << "set_sparse_lr needs set_gpu_sparse_handle first";
+    sparse_->set_lr(lr);
+  }
 
   // fn(meta: dict, keys: ndarray[u64], vals: ndarray[f32]) -> ndarray[f32] | None
   void SetPythonHandle(py::function fn) {
@@ -567,10 +594,14 @@ PYBIND11_MODULE(_core, m) {
       .def("set_gpu_dense_handle", &PyKVServer::SetGpuDenseHandle, py::arg("mode") = "assign",
            py::arg("dtype") = "f32")
       .def("set_gpu_sparse_handle", &PyKVServer::SetGpuSparseHandle, py::arg("rows"),
-           py::arg("row_len"), py::arg("accumulate") = true, py::arg("key_shift") = 0)
+           py::arg("row_len"), py::arg("accumulate") = true, py::arg("key_shift") = 0,
+           py::arg("optimizer") = py::none(), py::arg("lr") = 0.01f, py::arg("eps") = 1e-8f,
+           py::arg("init_acc") = 0.0f)
       .def("register_entry", &PyKVServer::RegisterEntry, py::arg("key"), py::arg("ptr"),
            py::arg("nbytes"), py::arg("device") = 0)
       .def("sparse_table_ptr", &PyKVServer::SparseTablePtr)
+      .def("sparse_state_ptr", &PyKVServer::SparseStatePtr)
+      .def("set_sparse_lr", &PyKVServer::SetSparseLr, py::arg("lr"))
       .def("save_checkpoint", &PyKVServer::SaveCheckpoint)
       .def("load_checkpoint", &PyKVServer::LoadCheckpoint)
       .def("set_python_handle", &PyKVServer::SetPythonHandle);
@@ -1111,6 +1142,22 @@ PYBIND11_MODULE(_core, m) {
           gpu::DeviceSync(-1);
         },
         py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
+  // one Adagrad step over the rows (kernels.h); out = 0: no gather. lr or
+  // eps <= 0 raises ValueError before any GPU call.
+  m.def("k_sparse_adagrad_f32",
+        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+           uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise, int key_shift,
+           uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseAdagradF32(reinterpret_cast<float*>(table), reinterpret_cast<float*>(state),
+                                 reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                 reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out), lr,
+                                 eps, rowwise, nullptr, key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
         py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
         py::arg("grid_cap") = 0);
 

@@ -723,13 +723,22 @@ void GpuDenseHandler::Load(const std::string& path) {
 // ----------------------------------------------------------------- sparse
 
 GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, bool accumulate,
-                                   int key_shift)
-    : po_(po), rows_(rows), row_len_(row_len), accumulate_(accumulate), key_shift_(key_shift) {
+                                   int key_shift, SparseOptConfig opt)
+    : po_(po),
+      rows_(rows),
+      row_len_(row_len),
+      accumulate_(accumulate),
+      key_shift_(key_shift),
+      opt_(opt),
+      lr_(opt.lr) {
   auto* pool = HbmPool::Get();
   XPS_CHECK(pool->initialized()) << "GpuSparseHandler needs the HBM pool";
+  bool has_opt = opt_.kind != SparseOpt::kNone;
   // concurrent workers scatter on different peer streams: accumulate
-  // must be element-atomic or overlapping rows lose updates
-  atomic_ = po_->num_workers() > 1;
+  // must be element-atomic or overlapping rows lose updates. An optimizer
+  // handler orders whole kernels instead (chain_).
+  atomic_ = po_->num_workers() > 1 && !has_opt;
+  chain_ = po_->num_workers() > 1 && has_opt;
   if (key_shift_ > 0) {
     int rank = po_->my_rank();
     // the first row whose key (row << key_shift) lies in our range. Range
@@ -743,6 +752,24 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
   XPS_HIP_CHECK(hipSetDevice(pool->device()));
   table_ = pool->AllocArray(rows * row_len * sizeof(float));
   XPS_HIP_CHECK(hipMemset(table_.data(), 0, table_.size()));
+  if (has_opt) {
+    state_ = pool->AllocArray(state_floats() * sizeof(float));
+    ResetState();
+  }
+}
+
+void GpuSparseHandler::ResetState() {
+  std::vector<float> host(state_floats(), opt_.init_acc);
+  XPS_HIP_CHECK(hipMemcpy(state_.data(), host.data(), host.size() * sizeof(float),
+                          hipMemcpyHostToDevice));
+}
+
+void GpuSparseHandler::OrderAfter(hipStream_t s) {
+  if (chain_ && last_ev_) XPS_HIP_CHECK(hipStreamWaitEvent(s, last_ev_.get(), 0));
+}
+
+void GpuSparseHandler::Publish(hipStream_t s) {
+  if (chain_) last_ev_ = MakeEventRef(po_, s);
 }
 
 hipStream_t GpuSparseHandler::Stream(int sender) {
@@ -767,12 +794,8 @@ const uint64_t* GpuSparseHandler::DeviceKeys(const SArray<Key>& keys, int sender
   return reinterpret_cast<const uint64_t*>(scratch.data());
 }
 
-// gather the n rows on `stream` and answer the pull with them
-void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n,
-                                     hipStream_t stream, KVServer<float>* server) {
-  SArray<char> out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
-  kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
-                        reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_, rows_);
+void GpuSparseHandler::RespondRows(const KVMeta& req, const SArray<char>& out, size_t n,
+                                   hipStream_t stream, KVServer<float>* server) {
   KVPairs<float> res;
   // keys stay meta-only: device keys must not be dereferenced host-side
   res.vals = SArray<float>::View(out);
@@ -783,6 +806,58 @@ void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, si
   // HbmDest also drains for a host-pool destination
   if (!(req.option & kOptPullAddr)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
   server->Response(req, res);
+}
+
+// gather the n rows on `stream` and answer the pull with them
+void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n,
+                                     hipStream_t stream, KVServer<float>* server) {
+  SArray<char> out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
+  OrderAfter(stream);
+  kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
+                        reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_, rows_);
+  Publish(stream);
+  RespondRows(req, out, n, stream, server);
+}
+
+void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kvs,
+                                     const uint64_t* rows, hipStream_t stream,
+                                     KVServer<float>* server) {
+  size_t n = kvs.keys.size();
+  float* table = reinterpret_cast<float*>(table_.data());
+  XPS_CHECK(req.cmd == kCmdDefault || req.cmd == kCmdAssign || req.cmd == kCmdSum)
+      << "optimizer sparse handler: cmd " << req.cmd << " names no operation";
+  if (req.cmd == kCmdDefault) {
+    // the gradient step; a fused round takes its response rows from the
+    // same launch
+    SArray<char> out;
+    if (req.pull) out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
+    OrderAfter(stream);
+    float* out_rows = req.pull ? reinterpret_cast<float*>(out.data()) : nullptr;
+    kern::SparseAdagradF32(table, reinterpret_cast<float*>(state_.data()), rows, n, row_len_,
+                           kvs.vals.data(), out_rows, lr_.load(std::memory_order_relaxed),
+                           opt_.eps, rowwise(), stream, key_shift_, row_base_, rows_);
+    Publish(stream);
+    if (req.pull) {
+      RespondRows(req, out, n, stream, server);
+      return;
+    }
+  } else {
+    OrderAfter(stream);
+    if (req.cmd == kCmdSum) {
+      kern::SparseScatterAddF32(table, rows, n, row_len_, kvs.vals.data(), /*atomic=*/false, stream,
+                                key_shift_, row_base_, rows_);
+    } else {
+      kern::SparseScatterAssignF32(table, rows, n, row_len_, kvs.vals.data(), stream, key_shift_,
+                                   row_base_, rows_);
+    }
+    Publish(stream);
+    if (req.pull) {
+      GatherRespond(req, rows, n, stream, server);
+      return;
+    }
+  }
+  if (!ThePlane(po_)) XPS_HIP_CHECK(hipStreamSynchronize(stream));
+  server->Response(req);
 }
 
 void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
@@ -796,6 +871,10 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
     XPS_CHECK(kvs.vals.on_device()) << "sparse push needs device vals (pool buffers)";
     XPS_CHECK_EQ(kvs.vals.size(), n * row_len_);
     const uint64_t* rows = DeviceKeys(kvs.keys, req.sender, stream);
+    if (opt_.kind != SparseOpt::kNone) {
+      OptimizerPush(req, kvs, rows, stream, server);
+      return;
+    }
     if (accumulate_ || req.cmd == kCmdSum) {
       kern::SparseScatterAddF32(table, rows, n, row_len_, kvs.vals.data(), atomic_,
                                 stream, key_shift_, row_base_, rows_);
@@ -824,6 +903,13 @@ void GpuSparseHandler::Save(const std::string& path) {
   std::vector<char> host(table_.size());
   XPS_HIP_CHECK(hipMemcpy(host.data(), table_.data(), table_.size(), hipMemcpyDeviceToHost));
   fwrite(host.data(), 1, host.size(), f);
+  if (opt_.kind != SparseOpt::kNone) {
+    uint64_t nstate = state_floats();
+    fwrite(&nstate, 8, 1, f);
+    host.resize(state_.size());
+    XPS_HIP_CHECK(hipMemcpy(host.data(), state_.data(), state_.size(), hipMemcpyDeviceToHost));
+    fwrite(host.data(), 1, host.size(), f);
+  }
   fclose(f);
 }
 
@@ -837,6 +923,17 @@ void GpuSparseHandler::Load(const std::string& path) {
   std::vector<char> host(table_.size());
   XPS_CHECK_EQ(fread(host.data(), 1, host.size(), f), host.size());
   XPS_HIP_CHECK(hipMemcpy(table_.data(), host.data(), table_.size(), hipMemcpyHostToDevice));
+  if (opt_.kind != SparseOpt::kNone) {
+    uint64_t nstate = 0;
+    if (fread(&nstate, 8, 1, f) == 1) {
+      XPS_CHECK_EQ(nstate, state_floats());
+      host.resize(state_.size());
+      XPS_CHECK_EQ(fread(host.data(), 1, host.size(), f), host.size());
+      XPS_HIP_CHECK(hipMemcpy(state_.data(), host.data(), state_.size(), hipMemcpyHostToDevice));
+    } else {
+      ResetState();  // a file that ends after the table: a fresh optimizer
+    }
+  }
   fclose(f);
 }
 

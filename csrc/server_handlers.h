@@ -167,6 +167,21 @@ class GpuDenseHandler {
 // row (ps-lite's sorted-unique key contract); duplicate rows across
 // MESSAGES are fine (atomic scatters with >1 workers; handler-serialized
 // otherwise).
+//
+// With an optimizer the handler keeps the optimizer state beside the table
+// and the push's cmd names the operation: kCmdDefault = one gradient step
+// (kern::SparseAdagradF32; state updated), kCmdAssign = assign rows (how
+// weights are initialised; state untouched), kCmdSum = add (state
+// untouched). `accumulate` plays no part then.
+enum class SparseOpt { kNone, kAdagrad, kRowwiseAdagrad };
+
+struct SparseOptConfig {
+  SparseOpt kind = SparseOpt::kNone;
+  float lr = 0.01f;
+  float eps = 1e-8f;
+  float init_acc = 0.f;  // the state's value before the first step
+};
+
 class GpuSparseHandler {
  public:
   // Allocates (and zeroes) a rows x row_len fp32 table shard in the pool.
@@ -174,9 +189,16 @@ class GpuSparseHandler {
   // slicer shards rows evenly; this server's local row =
   // (key >> key_shift) - row_base, row_base derived from its key range.
   GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, bool accumulate,
-                   int key_shift = 0);
+                   int key_shift = 0, SparseOptConfig opt = SparseOptConfig());
   void operator()(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   uintptr_t table_ptr() const { return reinterpret_cast<uintptr_t>(table_.data()); }
+  // the optimizer state (rows floats row-wise, else the table's shape); 0 without one
+  uintptr_t state_ptr() const { return reinterpret_cast<uintptr_t>(state_.data()); }
+  // learning rate of the gradient steps handled after the call
+  void set_lr(float lr) { lr_.store(lr, std::memory_order_relaxed); }
+  // Checkpoint: u64 rows, row_len, key_shift, then the table; with an
+  // optimizer u64 state_floats and the state follow. Loading a file that
+  // ends after the table resets the state to init_acc.
   void Save(const std::string& path);
   void Load(const std::string& path);
 
@@ -187,6 +209,19 @@ class GpuSparseHandler {
   const uint64_t* DeviceKeys(const SArray<Key>& keys, int sender, hipStream_t s);
   void GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n, hipStream_t stream,
                      KVServer<float>* server);
+  // answer a pull with the n rows that kernels on `stream` write into `out`
+  void RespondRows(const KVMeta& req, const SArray<char>& out, size_t n, hipStream_t stream,
+                   KVServer<float>* server);
+  // the push of an optimizer handler; with req.pull it answers the pull too
+  void OptimizerPush(const KVMeta& req, const KVPairs<float>& kvs, const uint64_t* rows,
+                     hipStream_t stream, KVServer<float>* server);
+  bool rowwise() const { return opt_.kind == SparseOpt::kRowwiseAdagrad; }
+  size_t state_floats() const { return rowwise() ? rows_ : rows_ * row_len_; }
+  void ResetState();  // state = init_acc, synchronously
+  // chain_: every kernel that touches the table waits for the one before
+  // it (OrderAfter) and leaves its event for the next (Publish)
+  void OrderAfter(hipStream_t s);
+  void Publish(hipStream_t s);
 
   Postoffice* po_;
   size_t rows_;
@@ -196,6 +231,16 @@ class GpuSparseHandler {
   int key_shift_ = 0;
   uint64_t row_base_ = 0;
   SArray<char> table_;
+  SparseOptConfig opt_;
+  std::atomic<float> lr_{0.f};
+  SArray<char> state_;
+  // optimizer with > 1 workers: a step is a read-modify-write that atomics
+  // cannot make safe, and the workers' messages run on different peer
+  // streams, so one event orders every kernel on the table (the dense
+  // handler's per-entry chain with the table as the one entry). A
+  // message's step is then atomic with respect to other messages.
+  bool chain_ = false;
+  EventRef last_ev_;
   std::mutex mu_;
   std::unordered_map<int, SArray<char>> key_scratch_;  // per sender
   hipStream_t fallback_stream_ = nullptr;

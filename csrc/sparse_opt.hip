@@ -1,0 +1,204 @@
+// Server-side optimizer step of the sparse handler for CDNA4 (gfx950):
+// Adagrad and row-wise Adagrad over the pushed rows of an embedding
+// table, with the post-update rows optionally written to a second
+// destination in the same pass (the fused ZPushPull round: no gather
+// launch, no second read of the table).
+//
+// Work split, wave64, no LDS. A row belongs to a group of G lanes, G the
+// smallest power of two >= the row's vectors (float4, or float on the
+// scalar path), at most 64; a wave serves 64 / G rows per step and waves
+// take sets of rows in a grid-stride loop. The loop bound is the same for
+// every lane of a wave, so lanes without a row or without a column (a
+// short last set, a row whose vector count is no power of two, a key
+// outside the table) stay in the loop and give zero to the cross-lane
+// sum. The gradient row is read once and kept in registers for the
+// update (kKeep vectors per lane: rows up to 1024 floats on the float4
+// path); vectors past that are read a second time. The row's state is
+// read and written by the group's first lane and handed to the others by
+// a shuffle. The element-wise variant has no reduction: the same body
+// with the shuffles compiled out and the state moved like the table.
+#include <hip/hip_runtime.h>
+
+#include <stdexcept>
+
+#include "kernels.h"
+
+namespace xps {
+namespace kern {
+
+namespace {
+
+constexpr int kKeep = 4;  // gradient vectors a lane keeps between the two passes
+
+__device__ inline float SumSq(float v) { return v * v; }
+__device__ inline float SumSq(float4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+
+// IEEE multiply, square root, add, divide and subtract, in that order:
+// the tests' error bound counts one rounding for each
+__device__ inline float Step(float w, float g, float lr, float denom) {
+  return w - (lr * g) / denom;
+}
+__device__ inline float Denom(float s, float eps) { return sqrtf(s) + eps; }
+
+// new weights of one vector given a ready denominator (row-wise)
+__device__ inline float Update(float w, float g, float lr, float denom) {
+  return Step(w, g, lr, denom);
+}
+__device__ inline float4 Update(float4 w, float4 g, float lr, float denom) {
+  return float4{Step(w.x, g.x, lr, denom), Step(w.y, g.y, lr, denom), Step(w.z, g.z, lr, denom),
+                Step(w.w, g.w, lr, denom)};
+}
+
+// element-wise: *s += g * g, then the step under the element's own state
+__device__ inline float UpdateElem(float w, float g, float* s, float lr, float eps) {
+  *s += g * g;
+  return Step(w, g, lr, Denom(*s, eps));
+}
+__device__ inline float4 UpdateElem(float4 w, float4 g, float4* s, float lr, float eps) {
+  return float4{UpdateElem(w.x, g.x, &s->x, lr, eps), UpdateElem(w.y, g.y, &s->y, lr, eps),
+                UpdateElem(w.z, g.z, &s->z, lr, eps), UpdateElem(w.w, g.w, &s->w, lr, eps)};
+}
+
+struct AdagradArgs {
+  const uint64_t* rows;
+  size_t nrows;
+  size_t nv;      // vectors per row
+  float row_len;  // floats per row: the divisor of the row-wise mean
+  float lr;
+  float eps;
+  int log2g;  // G = 1 << log2g lanes per row
+  int shift;
+  uint64_t base;
+  uint64_t tab_rows;
+};
+
+template <class V, bool kRowwise>
+__global__ void __launch_bounds__(kBlock)
+    sparse_adagrad_kernel(V* __restrict__ table, float* __restrict__ state,
+                          const V* __restrict__ grad, V* __restrict__ out, AdagradArgs a) {
+  const int G = 1 << a.log2g;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane & (G - 1);  // lane within the row's group
+  const size_t rows_per_wave = 64 >> a.log2g;
+  const size_t tid = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  const size_t wave = tid >> 6;
+  const size_t nwaves = (static_cast<size_t>(gridDim.x) * blockDim.x) >> 6;
+  const size_t nv = a.nv;
+  const size_t resident = static_cast<size_t>(kKeep) << a.log2g;  // vectors the registers hold
+  const V zero{};
+
+  // wave-uniform bounds: every lane of the wave reaches the shuffles
+  for (size_t first = wave * rows_per_wave; first < a.nrows; first += nwaves * rows_per_wave) {
+    const size_t r = first + (lane >> a.log2g);
+    const bool live = r < a.nrows;
+    const uint64_t row = live ? (a.rows[r] >> a.shift) - a.base : ~0ull;
+    const bool ok = live && row < a.tab_rows;  // unsigned: also catches keys below base
+    const V* gp = grad + (live ? r * nv : 0);
+    V* tp = table + (ok ? row * nv : 0);
+
+    V g[kKeep];
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < kKeep; ++k) {
+      const size_t c = gl + (static_cast<size_t>(k) << a.log2g);
+      g[k] = (ok && c < nv) ? gp[c] : zero;
+      if (kRowwise) ss += SumSq(g[k]);
+    }
+
+    float denom = 0.f;
+    if (kRowwise) {
+      if (ok) {
+        for (size_t c = resident + gl; c < nv; c += G) ss += SumSq(gp[c]);
+      }
+      for (int m = G >> 1; m > 0; m >>= 1) ss += __shfl_xor(ss, m);
+      float s = 0.f;
+      if (ok && gl == 0) {
+        s = state[row] + ss / a.row_len;
+        state[row] = s;
+      }
+      s = __shfl(s, lane - gl);
+      denom = Denom(s, a.eps);
+    }
+
+    if (!live) continue;  // past the shuffles: nothing below crosses lanes
+    if (!ok) {
+      // the gather's defined output for a key outside the table
+      if (out) {
+        for (size_t c = gl; c < nv; c += G) out[r * nv + c] = zero;
+      }
+      continue;
+    }
+    V* sp = kRowwise ? nullptr : reinterpret_cast<V*>(state) + row * nv;
+    auto apply = [&](size_t c, V gv) {
+      V w;
+      if (kRowwise) {
+        w = Update(tp[c], gv, a.lr, denom);
+      } else {
+        V s = sp[c];
+        w = UpdateElem(tp[c], gv, &s, a.lr, a.eps);
+        sp[c] = s;
+      }
+      tp[c] = w;
+      if (out) out[r * nv + c] = w;
+    };
+#pragma unroll
+    for (int k = 0; k < kKeep; ++k) {
+      const size_t c = gl + (static_cast<size_t>(k) << a.log2g);
+      if (c < nv) apply(c, g[k]);
+    }
+    for (size_t c = resident + gl; c < nv; c += G) apply(c, gp[c]);
+  }
+}
+
+template <class V, bool kRowwise>
+void LaunchAdagrad(float* table, float* state, const float* grad, float* out, AdagradArgs a,
+                   int grid_cap, hipStream_t s) {
+  while ((size_t{1} << a.log2g) < a.nv && a.log2g < 6) ++a.log2g;
+  size_t rows_per_wave = 64 >> a.log2g;
+  size_t waves = (a.nrows + rows_per_wave - 1) / rows_per_wave;
+  // the sparse kernels' grid: enough blocks for the 8 XCDs, at most 16384
+  int grid = GridFor(waves * 64, 16384, grid_cap);
+  hipLaunchKernelGGL((sparse_adagrad_kernel<V, kRowwise>), dim3(grid), dim3(kBlock), 0, s,
+                     reinterpret_cast<V*>(table), state, reinterpret_cast<const V*>(grad),
+                     reinterpret_cast<V*>(out), a);
+}
+
+}  // namespace
+
+void SparseAdagradF32(float* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                      size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
+                      bool rowwise, hipStream_t s, int key_shift, uint64_t row_base,
+                      uint64_t table_rows, int grid_cap) {
+  if (!(lr > 0.f)) throw std::invalid_argument("SparseAdagradF32: lr must be positive");
+  if (!(eps > 0.f)) throw std::invalid_argument("SparseAdagradF32: eps must be positive");
+  if (nrows == 0 || row_len == 0) return;
+  AdagradArgs a{};
+  a.rows = rows_dev;
+  a.nrows = nrows;
+  a.nv = row_len;
+  a.row_len = static_cast<float>(row_len);
+  a.lr = lr;
+  a.eps = eps;
+  a.shift = key_shift;
+  a.base = row_base;
+  a.tab_rows = table_rows;
+  // float4 needs whole vectors and every array it moves on a 16 B boundary
+  // (the row-wise state moves as single floats)
+  bool vec = row_len % 4 == 0 && Aligned16(table, grad, out_or_null) &&
+             (rowwise || Aligned16(state));
+  if (vec) {
+    a.nv = row_len / 4;
+    if (rowwise) {
+      LaunchAdagrad<float4, true>(table, state, grad, out_or_null, a, grid_cap, s);
+    } else {
+      LaunchAdagrad<float4, false>(table, state, grad, out_or_null, a, grid_cap, s);
+    }
+  } else if (rowwise) {
+    LaunchAdagrad<float, true>(table, state, grad, out_or_null, a, grid_cap, s);
+  } else {
+    LaunchAdagrad<float, false>(table, state, grad, out_or_null, a, grid_cap, s);
+  }
+}
+
+}  // namespace kern
+}  // namespace xps

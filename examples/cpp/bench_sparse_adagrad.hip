@@ -1,0 +1,124 @@
+// One-process timing of the fused Adagrad step (csrc/sparse_opt.hip)
+// against the launches it replaces in a fused sparse round, the
+// scatter-add and the gather of csrc/kernels.hip, on the same buffers.
+// Links kernels.hip and sparse_opt.hip only: no cluster, no Python.
+//
+//   build/bench_sparse_adagrad [--rounds N]
+//
+// Shape: the sparse bench config, a 1M x 64 fp32 table with 8192 unique
+// rows per step. Two key schedules: "hot", the same 8192 rows every step
+// (what the bench does: the rows stay in cache), and "rotating", 64
+// disjoint sets of 8192 rows taken in turn (128 MiB of table rows between
+// two visits of a set). Every round times, each between its own pair of
+// HIP events and in alternation:
+//   fused   SparseAdagradF32, row-wise, with out  (one launch)
+//   pair    SparseScatterAddF32 + SparseGatherF32 (two launches)
+// Output: median, 10th and 90th percentile of each in microseconds.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../csrc/kernels.h"
+
+#define CHECK(x)                                                                       \
+  do {                                                                                 \
+    hipError_t e_ = (x);                                                               \
+    if (e_ != hipSuccess) {                                                            \
+      fprintf(stderr, "%s:%d: %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
+      exit(1);                                                                         \
+    }                                                                                  \
+  } while (0)
+
+namespace {
+
+constexpr size_t kRows = 1u << 20, kRowLen = 64, kHot = 8192, kSets = 64;
+
+__global__ void fill_kernel(float* p, size_t n, unsigned salt, float scale) {
+  size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < n; i += stride) {
+    unsigned x = (static_cast<unsigned>(i) + salt) * 2654435761u;
+    x ^= x >> 15;
+    p[i] = scale * static_cast<float>(static_cast<int>(x & 0xffffu) - 32768) / 32768.0f;
+  }
+}
+
+void Report(const char* schedule, const char* name, std::vector<float>* us) {
+  std::sort(us->begin(), us->end());
+  size_t n = us->size();
+  printf("%-9s %-6s %9.2f %9.2f %9.2f\n", schedule, name, (*us)[n / 2], (*us)[n / 10],
+         (*us)[n * 9 / 10]);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  int rounds = 500;
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "--rounds") && i + 1 < argc) {
+      rounds = atoi(argv[++i]);
+    } else {
+      fprintf(stderr, "usage: %s [--rounds N]\n", argv[0]);
+      return 2;
+    }
+  }
+  if (rounds < 10) return 2;
+
+  float *table, *state, *grad, *out;
+  uint64_t* keys;
+  CHECK(hipMalloc(reinterpret_cast<void**>(&table), kRows * kRowLen * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&state), kRows * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&grad), kHot * kRowLen * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&out), kHot * kRowLen * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&keys), kSets * kHot * 8));
+  hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, nullptr, table, kRows * kRowLen, 1u,
+                     1.0f);
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, nullptr, grad, kHot * kRowLen, 2u, 1e-3f);
+  CHECK(hipMemset(state, 0, kRows * 4));
+  // an odd multiplier permutes the 2^20 rows: the sets are disjoint and
+  // every row of a set is unique
+  std::vector<uint64_t> h(kSets * kHot);
+  for (size_t i = 0; i < h.size(); ++i) h[i] = (i * 668265261u + 12345u) & (kRows - 1);
+  CHECK(hipMemcpy(keys, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  CHECK(hipDeviceSynchronize());
+
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  printf("# %zu x %zu table, %zu rows per step, %d rounds, microseconds\n", kRows, kRowLen, kHot,
+         rounds);
+  printf("%-9s %-6s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
+  for (int rotating = 0; rotating < 2; ++rotating) {
+    std::vector<float> us_fused, us_pair;
+    for (int r = -20; r < rounds; ++r) {
+      const uint64_t* k = keys + (rotating ? (static_cast<size_t>(r + 20) % kSets) * kHot : 0);
+      float ms = 0;
+      CHECK(hipEventRecord(e0, nullptr));
+      xps::kern::SparseAdagradF32(table, state, k, kHot, kRowLen, grad, out, 0.01f, 1e-8f,
+                                  /*rowwise=*/true, nullptr, 0, 0, kRows);
+      CHECK(hipEventRecord(e1, nullptr));
+      CHECK(hipEventSynchronize(e1));
+      CHECK(hipEventElapsedTime(&ms, e0, e1));
+      if (r >= 0) us_fused.push_back(ms * 1000.f);
+      // the pair visits the set half a turn away, as cold as the fused
+      // launch found its own
+      if (rotating) k = keys + (static_cast<size_t>(r + 20 + kSets / 2) % kSets) * kHot;
+      CHECK(hipEventRecord(e0, nullptr));
+      xps::kern::SparseScatterAddF32(table, k, kHot, kRowLen, grad, /*atomic=*/false, nullptr, 0,
+                                     0, kRows);
+      xps::kern::SparseGatherF32(table, k, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+      CHECK(hipEventRecord(e1, nullptr));
+      CHECK(hipEventSynchronize(e1));
+      CHECK(hipEventElapsedTime(&ms, e0, e1));
+      if (r >= 0) us_pair.push_back(ms * 1000.f);
+    }
+    CHECK(hipGetLastError());
+    Report(rotating ? "rotating" : "hot", "fused", &us_fused);
+    Report(rotating ? "rotating" : "hot", "pair", &us_pair);
+  }
+  return 0;
+}

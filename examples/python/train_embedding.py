@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Embedding-bag regression with the optimizer on the server: the table
+lives in the sparse handler, row-wise Adagrad runs there, and a training
+step is ONE fused zpushpull_ptr.
+
+Each sample is a bag of row ids whose embeddings are summed and regressed
+onto the sum of a hidden table's rows. A step's message carries the
+gradients of the current batch and, with zero gradients (a zero step), the
+rows the next batch will read; the response is those rows after the
+update, so the next forward pass needs no pull of its own. Duplicate ids
+are coalesced on the worker (torch.unique + index_add_): the handler wants
+unique rows in a message.
+
+Needs one MI355X.  Run:  python examples/python/train_embedding.py
+"""
+import sys
+import threading
+
+import numpy as np
+
+sys.path.insert(0, __file__.rsplit("/examples/", 1)[0])
+import ps_lite_amd as ps  # noqa: E402
+
+ROWS, DIM, BATCH, BAG, STEPS = 512, 32, 256, 4, 60
+
+
+def main():
+    import torch
+
+    ps.setup_env(1, 1, root_port=9310, XPS_DEV_ID=0, XPS_POOL_GB=1)
+    roles = (("scheduler", -1), ("joint", 0))
+    ths = [threading.Thread(target=ps.start, kwargs=dict(role=r, device=d)) for r, d in roles]
+    [t.start() for t in ths]
+    [t.join() for t in ths]
+    server = ps.KVServer(0)
+    server.set_gpu_sparse_handle(ROWS, DIM, optimizer="rowwise_adagrad", lr=0.1, eps=1e-8)
+    worker = ps.KVWorker(0, 0)
+
+    gen = torch.Generator().manual_seed(3)
+    hidden = torch.randn(ROWS, DIM, generator=gen).cuda()
+    bags = torch.randint(0, ROWS, (STEPS + 1, BATCH, BAG), generator=gen).cuda()
+    cap = 2 * BATCH * BAG  # rows of two batches at the most
+    vals, out = ps.pool_tensor((cap, DIM)), ps.pool_tensor((cap, DIM))
+
+    def round_trip(ids, grads, cmd=0):
+        """push grads for the sorted unique ids, return their rows afterwards"""
+        n = ids.numel()
+        vals[:n] = grads
+        torch.cuda.synchronize()
+        keys = ids.cpu().numpy().astype(np.uint64)
+        lens = np.full(n, DIM, dtype=np.int32)
+        worker.wait(worker.zpushpull_ptr(keys, vals.data_ptr(), out.data_ptr(), n * DIM * 4, 0,
+                                         lens, cmd=cmd))
+        return out[:n].clone()
+
+    every = torch.arange(ROWS, device="cuda")
+    round_trip(every, 0.1 * torch.randn(ROWS, DIM, generator=gen).cuda(), cmd=1)  # initial weights
+    ids = torch.unique(bags[0])
+    rows = round_trip(ids, torch.zeros(ids.numel(), DIM, device="cuda"))  # a zero step: a pull
+    losses = []
+    for step in range(STEPS):
+        bag = bags[step]
+        at = torch.searchsorted(ids, bag)  # where each id's row sits in `rows`
+        err = rows[at].sum(dim=1) - hidden[bag].sum(dim=1)
+        losses.append(float((err * err).mean()))
+        # d loss / d row, one term per occurrence, coalesced per unique id
+        # of this batch and the next
+        ids = torch.unique(torch.cat([bag.flatten(), bags[step + 1].flatten()]))
+        per_use = (2.0 / err.numel()) * err[:, None, :].expand(BATCH, BAG, DIM)
+        grads = torch.zeros(ids.numel(), DIM, device="cuda")
+        grads.index_add_(0, torch.searchsorted(ids, bag.flatten()), per_use.reshape(-1, DIM))
+        rows = round_trip(ids, grads)
+        if step % 10 == 0 or step == STEPS - 1:
+            print("step %2d  loss %.4f" % (step, losses[-1]))
+
+    ths = [threading.Thread(target=ps.finalize, kwargs=dict(role=r)) for r, _ in roles]
+    [t.start() for t in ths]
+    [t.join() for t in ths]
+    assert losses[-1] < 0.5 * losses[0], "the loss did not fall"
+    print("loss %.4f -> %.4f with row-wise Adagrad on the server" % (losses[0], losses[-1]))
+
+
+if __name__ == "__main__":
+    main()
