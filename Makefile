@@ -49,6 +49,8 @@ build/%.hip.o: %.hip csrc/*.h
 # the optimizer kernels keep fp32 operations unpaired: every multiply, add
 # and divide rounds once, as their error bound counts them
 build/csrc/sparse_opt.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# the coalescer's row sums likewise: one unpaired IEEE add per occurrence
+build/csrc/sparse_coalesce.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(TARGET): $(OBJS)
 	$(HIPCC) $(LDFLAGS) $(OBJS) -o $@

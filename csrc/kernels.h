@@ -82,6 +82,31 @@ void SparseAdagradF32(float* table, float* state, const uint64_t* rows_dev, size
                       size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
                       bool rowwise, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
                       uint64_t table_rows = ~0ull, int grid_cap = 0);
+// Worker side of the sparse ops (sparse_coalesce.hip): a batch's ids, in any
+// order and with any repetition, become the sorted unique keys the ops above
+// and the handlers want. ids compare as unsigned 64-bit values.
+//   uniq_keys[0, m): the distinct ids, strictly ascending, each << key_shift
+//   inverse[i]:      the slot in [0, m) of ids[i], for every i < n
+//   sums[u]:         +0.0, then + grad[i] for every i < grad_rows with
+//                    inverse[i] == u, in ascending i, one IEEE fp32 add each
+//                    (np.add.at on a zero array, bit for bit); occurrences
+//                    i >= grad_rows name a row without a gradient
+// Returns m after synchronising s. uniq_keys and inverse have n slots, sums
+// n x row_len (rows past m are not written); grad_or_null = null gives rows
+// of +0.0, sums_or_null = null skips the sums. Rows move as float4 when
+// row_len % 4 == 0 and grad and sums are 16 B-aligned, else as floats.
+// n == 0 returns 0 without a HIP call. std::invalid_argument before any HIP
+// call: n >= 2^31, grad_rows > n, a gradient with row_len == 0, a workspace
+// below SparseCoalesceWorkspaceBytes(n), key_shift outside [0, 63], and
+// ids, uniq_keys or inverse off an 8 B boundary.
+// Limit: one group of lanes sums a whole segment, so one very hot id in a
+// huge batch serialises; splitting a segment would change the add order.
+int SparseCoalesceTile();  // elements a block sorts in LDS
+size_t SparseCoalesceWorkspaceBytes(size_t n);
+size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const float* grad_or_null,
+                      size_t grad_rows, size_t row_len, uint64_t* uniq_keys, float* sums_or_null,
+                      int64_t* inverse, void* workspace, size_t workspace_bytes, hipStream_t s,
+                      int grid_cap = 0);
 
 // Batched segmented copy/accumulate: one launch serving up to
 // kMaxBatch (dst, src, nbytes) segments — the device-side slicing/merge

@@ -1160,6 +1160,25 @@ PYBIND11_MODULE(_core, m) {
         py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
         py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
         py::arg("grid_cap") = 0);
+  // ids -> sorted unique keys, summed rows, slot per occurrence (kernels.h);
+  // returns the number of unique keys. grad = 0: no gradients, sums = 0: no
+  // sums. A bad argument raises ValueError before any GPU call.
+  m.def("k_sparse_coalesce",
+        [](uintptr_t ids, size_t n, int key_shift, uintptr_t grad, size_t grad_rows,
+           size_t row_len, uintptr_t uniq_keys, uintptr_t sums, uintptr_t inverse,
+           uintptr_t workspace, size_t workspace_bytes, int grid_cap) {
+          return kern::SparseCoalesce(
+              reinterpret_cast<uint64_t*>(ids), n, key_shift, reinterpret_cast<float*>(grad),
+              grad_rows, row_len, reinterpret_cast<uint64_t*>(uniq_keys),
+              reinterpret_cast<float*>(sums), reinterpret_cast<int64_t*>(inverse),
+              reinterpret_cast<void*>(workspace), workspace_bytes, nullptr, grid_cap);
+        },
+        py::arg("ids"), py::arg("n"), py::arg("key_shift"), py::arg("grad"),
+        py::arg("grad_rows"), py::arg("row_len"), py::arg("uniq_keys"), py::arg("sums"),
+        py::arg("inverse"), py::arg("workspace"), py::arg("workspace_bytes"),
+        py::arg("grid_cap") = 0);
+  m.def("sparse_coalesce_workspace_bytes", &kern::SparseCoalesceWorkspaceBytes, py::arg("n"));
+  m.attr("coalesce_tile") = kern::SparseCoalesceTile();
 
   py::class_<PySimpleApp>(m, "SimpleApp")
       .def(py::init<const std::string&, int, int>(), py::arg("role"), py::arg("app_id") = 10,

@@ -7,9 +7,12 @@ Each sample is a bag of row ids whose embeddings are summed and regressed
 onto the sum of a hidden table's rows. A step's message carries the
 gradients of the current batch and, with zero gradients (a zero step), the
 rows the next batch will read; the response is those rows after the
-update, so the next forward pass needs no pull of its own. Duplicate ids
-are coalesced on the worker (torch.unique + index_add_): the handler wants
-unique rows in a message.
+update, so the next forward pass needs no pull of its own. The handler
+wants sorted unique rows in a message: one sparse_coalesce per step turns
+the ids of both batches and the per-occurrence gradients into the keys,
+the summed rows (written straight into the pool tensor) and the slot of
+every occurrence, and one sparse_gather turns the response back into
+per-occurrence rows.
 
 Needs one MI355X.  Run:  python examples/python/train_embedding.py
 """
@@ -20,6 +23,7 @@ import numpy as np
 
 sys.path.insert(0, __file__.rsplit("/examples/", 1)[0])
 import ps_lite_amd as ps  # noqa: E402
+from ps_lite_amd import ops  # noqa: E402
 
 ROWS, DIM, BATCH, BAG, STEPS = 512, 32, 256, 4, 60
 
@@ -42,10 +46,13 @@ def main():
     cap = 2 * BATCH * BAG  # rows of two batches at the most
     vals, out = ps.pool_tensor((cap, DIM)), ps.pool_tensor((cap, DIM))
 
-    def round_trip(ids, grads, cmd=0):
-        """push grads for the sorted unique ids, return their rows afterwards"""
+    keys_buf = torch.empty(cap, dtype=torch.int64, device="cuda")
+    scratch = torch.empty(ps._core.sparse_coalesce_workspace_bytes(cap), dtype=torch.uint8,
+                          device="cuda")
+
+    def round_trip(ids, cmd=0):
+        """push vals[:n] for the n sorted unique ids, return their rows afterwards"""
         n = ids.numel()
-        vals[:n] = grads
         torch.cuda.synchronize()
         keys = ids.cpu().numpy().astype(np.uint64)
         lens = np.full(n, DIM, dtype=np.int32)
@@ -53,23 +60,24 @@ def main():
                                          lens, cmd=cmd))
         return out[:n].clone()
 
-    every = torch.arange(ROWS, device="cuda")
-    round_trip(every, 0.1 * torch.randn(ROWS, DIM, generator=gen).cuda(), cmd=1)  # initial weights
-    ids = torch.unique(bags[0])
-    rows = round_trip(ids, torch.zeros(ids.numel(), DIM, device="cuda"))  # a zero step: a pull
+    vals[:ROWS] = 0.1 * torch.randn(ROWS, DIM, generator=gen).cuda()
+    round_trip(torch.arange(ROWS, device="cuda"), cmd=1)  # initial weights
+    ids, _, at = ops.sparse_coalesce(bags[0], out_keys=keys_buf, workspace=scratch)
+    vals[:ids.numel()] = 0.0
+    rows = round_trip(ids)  # a zero step: a pull
     losses = []
     for step in range(STEPS):
         bag = bags[step]
-        at = torch.searchsorted(ids, bag)  # where each id's row sits in `rows`
-        err = rows[at].sum(dim=1) - hidden[bag].sum(dim=1)
+        # `at`: where each occurrence's row sits in `rows`
+        err = ops.sparse_gather(rows, at).view(BATCH, BAG, DIM).sum(dim=1) - hidden[bag].sum(dim=1)
         losses.append(float((err * err).mean()))
-        # d loss / d row, one term per occurrence, coalesced per unique id
-        # of this batch and the next
-        ids = torch.unique(torch.cat([bag.flatten(), bags[step + 1].flatten()]))
-        per_use = (2.0 / err.numel()) * err[:, None, :].expand(BATCH, BAG, DIM)
-        grads = torch.zeros(ids.numel(), DIM, device="cuda")
-        grads.index_add_(0, torch.searchsorted(ids, bag.flatten()), per_use.reshape(-1, DIM))
-        rows = round_trip(ids, grads)
+        # d loss / d row, one term per occurrence of this batch; the message
+        # names the ids of this batch and the next, coalesced per unique id
+        per_use = ((2.0 / err.numel()) * err)[:, None, :].expand(BATCH, BAG, DIM).reshape(-1, DIM)
+        ids, _, inverse = ops.sparse_coalesce(bags[step:step + 2], grad=per_use, out_keys=keys_buf,
+                                              out_sums=vals, workspace=scratch)
+        at = inverse[BATCH * BAG:]  # the next batch's occurrences
+        rows = round_trip(ids)
         if step % 10 == 0 or step == STEPS - 1:
             print("step %2d  loss %.4f" % (step, losses[-1]))
 

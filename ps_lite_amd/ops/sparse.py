@@ -26,6 +26,45 @@ def sparse_scatter_add(table, rows, src, atomic=False):
     return table
 
 
+def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, workspace=None):
+    """Sorted unique keys, summed gradient rows and the slot of every id.
+
+    ids: int64 or uint64 CUDA tensor of any shape, any order, any repetition
+    (compared as unsigned). grad: (grad_rows, row_len) fp32, row i for
+    ids.flatten()[i]; ids past grad_rows carry no gradient. Returns
+    (keys[:m], sums[:m] or None, inverse): keys ascending, each
+    id << key_shift; sums[u] the rows of key u added in ascending i, bit for
+    bit the same on every run; inverse int64 with inverse[i] the slot of id i.
+    out_keys (>= n elements), out_sums (>= n rows of row_len) and workspace
+    (>= _core.sparse_coalesce_workspace_bytes(n) bytes) are optional
+    preallocated buffers; with all three nothing but inverse is allocated."""
+    import torch
+
+    assert ids.is_cuda and ids.dtype in (torch.int64, torch.uint64)
+    ids = ids.reshape(-1)  # a view of a contiguous tensor
+    n = ids.numel()
+    grad_rows, row_len = (0, 0) if grad is None else grad.shape
+    if grad is not None:
+        assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous()
+        if out_sums is None:
+            out_sums = torch.empty(n, row_len, device=ids.device, dtype=torch.float32)
+        assert out_sums.is_contiguous() and out_sums.dtype == torch.float32
+        assert out_sums.dim() == 2 and out_sums.shape[0] >= n and out_sums.shape[1] == row_len
+    if out_keys is None:
+        out_keys = torch.empty(n, device=ids.device, dtype=ids.dtype)
+    assert out_keys.is_contiguous() and out_keys.numel() >= n and out_keys.element_size() == 8
+    need = _core.sparse_coalesce_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(need, device=ids.device, dtype=torch.uint8)
+    ws_bytes = workspace.numel() * workspace.element_size()
+    inverse = torch.empty(n, device=ids.device, dtype=torch.int64)
+    m = _core.k_sparse_coalesce(ids.data_ptr(), n, key_shift,
+                                0 if grad is None else grad.data_ptr(), grad_rows, row_len,
+                                out_keys.data_ptr(), 0 if grad is None else out_sums.data_ptr(),
+                                inverse.data_ptr(), workspace.data_ptr(), ws_bytes)
+    return out_keys[:m], (None if grad is None else out_sums[:m]), inverse
+
+
 def sparse_adagrad(table, state, rows, grad, lr, eps=1e-8, out=None):
     """One Adagrad step on table[rows[i]] with gradient grad[i], in one launch.
 
