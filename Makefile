@@ -91,8 +91,9 @@ mxfp8bench: build/csrc/kernels.hip.o build/csrc/mxfp8.hip.o build/bench_mxfp8.o
 	$(HIPCC) $(CPPBENCH_LD) build/bench_mxfp8.o build/csrc/kernels.hip.o \
 	    build/csrc/mxfp8.hip.o -o build/bench_mxfp8
 
-# one-process timing of the fused Adagrad step against scatter-add + gather
-# (links kernels.hip and sparse_opt.hip only): build/bench_sparse_adagrad
+# one-process timing of the fused Adagrad step against scatter-add + gather,
+# or with --opt of a lazy-Adam step against the Adagrad step (links
+# kernels.hip and sparse_opt.hip only): build/bench_sparse_adagrad
 build/bench_sparse_adagrad.o: examples/cpp/bench_sparse_adagrad.hip csrc/*.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_sparse_adagrad.hip -o build/bench_sparse_adagrad.o

@@ -82,6 +82,28 @@ void SparseAdagradF32(float* table, float* state, const uint64_t* rows_dev, size
                       size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
                       bool rowwise, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
                       uint64_t table_rows = ~0ull, int grid_cap = 0);
+// Sparse ("lazy") Adam step on the rows r whose decoded row lies in the
+// table, g = grad[r] (sparse_opt.hip). The bias correction is the row's own:
+// p1, p2 are the running products beta1^t, beta2^t of that row's steps.
+//   p1' = p1 * beta1,  p2' = p2 * beta2
+//   m'  = beta1 * m + (1 - beta1) * g
+//   v'  = beta2 * v + (1 - beta2) * g * g                 (element-wise)
+//   v'  = beta2 * v + (1 - beta2) * sum(g * g) / row_len  (rowwise: one float per row)
+//   w'  = w - (lr / (1 - p1')) * m' / (sqrt(v' / (1 - p2')) + eps)
+// state holds one record per table row,
+//   { p1, p2, v_row, 0 }  m[row_len]  v[row_len] (element-wise only)
+// SparseLazyAdamStateFloats floats in all; a fresh state has p1 = p2 = 1 and
+// +0.0 everywhere else (v_row is unused element-wise). out_or_null, row
+// uniqueness, disjointness and rows outside the table are as for Adagrad.
+// Rows move as float4 when row_len % 4 == 0 and table, grad and out are
+// 16 B-aligned, else as single floats. lr <= 0, eps <= 0, a beta outside
+// [0, 1) or a state off a 16 B boundary is std::invalid_argument and nothing
+// is launched.
+size_t SparseLazyAdamStateFloats(size_t rows, size_t row_len, bool rowwise);
+void SparseLazyAdamF32(float* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                       size_t row_len, const float* grad, float* out_or_null, float lr, float beta1,
+                       float beta2, float eps, bool rowwise, hipStream_t s, int key_shift = 0,
+                       uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
 // Worker side of the sparse ops (sparse_coalesce.hip): a batch's ids, in any
 // order and with any repetition, become the sorted unique keys the ops above
 // and the handlers want. ids compare as unsigned 64-bit values.

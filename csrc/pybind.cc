@@ -329,10 +329,13 @@ class PyKVServer {
     });
   }
 
-  // optimizer: None, "adagrad" or "rowwise_adagrad". Bad arguments raise
-  // ValueError before the handler (and with it the GPU) is touched.
+  // optimizer: None, "adagrad", "rowwise_adagrad", "lazy_adam" or
+  // "rowwise_lazy_adam" (the sparse Adam with per-row bias correction; there
+  // is no dense "adam"). Bad arguments raise ValueError before the handler
+  // (and with it the GPU) is touched.
   void SetGpuSparseHandle(size_t rows, size_t row_len, bool accumulate, int key_shift,
-                          py::object optimizer, float lr, float eps, float init_acc) {
+                          py::object optimizer, float lr, float eps, float init_acc, float beta1,
+                          float beta2) {
     SparseOptConfig opt;
     if (!optimizer.is_none()) {
       std::string name = py::cast<std::string>(optimizer);
@@ -340,17 +343,29 @@ class PyKVServer {
         opt.kind = SparseOpt::kAdagrad;
       } else if (name == "rowwise_adagrad") {
         opt.kind = SparseOpt::kRowwiseAdagrad;
+      } else if (name == "lazy_adam") {
+        opt.kind = SparseOpt::kLazyAdam;
+      } else if (name == "rowwise_lazy_adam") {
+        opt.kind = SparseOpt::kRowwiseLazyAdam;
       } else {
-        throw py::value_error("optimizer must be None, \"adagrad\" or \"rowwise_adagrad\" (got \"" +
-                              name + "\")");
+        throw py::value_error(
+            "optimizer must be None, \"adagrad\", \"rowwise_adagrad\", \"lazy_adam\" or "
+            "\"rowwise_lazy_adam\" (got \"" + name + "\")");
       }
     }
     if (!(lr > 0.f)) throw py::value_error("lr must be positive");
     if (!(eps > 0.f)) throw py::value_error("eps must be positive");
     if (!(init_acc >= 0.f)) throw py::value_error("init_acc must not be negative");
+    if (opt.kind == SparseOpt::kLazyAdam || opt.kind == SparseOpt::kRowwiseLazyAdam) {
+      if (init_acc != 0.f) throw py::value_error("init_acc belongs to Adagrad: lazy Adam has none");
+      if (!(beta1 >= 0.f && beta1 < 1.f)) throw py::value_error("beta1 must lie in [0, 1)");
+      if (!(beta2 >= 0.f && beta2 < 1.f)) throw py::value_error("beta2 must lie in [0, 1)");
+    }
     opt.lr = lr;
     opt.eps = eps;
     opt.init_acc = init_acc;
+    opt.beta1 = beta1;
+    opt.beta2 = beta2;
     auto h = std::make_shared<GpuSparseHandler>(s_.postoffice(), rows, row_len, accumulate,
                                                 key_shift, opt);
     sparse_ = h;
@@ -596,7 +611,7 @@ PYBIND11_MODULE(_core, m) {
       .def("set_gpu_sparse_handle", &PyKVServer::SetGpuSparseHandle, py::arg("rows"),
            py::arg("row_len"), py::arg("accumulate") = true, py::arg("key_shift") = 0,
            py::arg("optimizer") = py::none(), py::arg("lr") = 0.01f, py::arg("eps") = 1e-8f,
-           py::arg("init_acc") = 0.0f)
+           py::arg("init_acc") = 0.0f, py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f)
       .def("register_entry", &PyKVServer::RegisterEntry, py::arg("key"), py::arg("ptr"),
            py::arg("nbytes"), py::arg("device") = 0)
       .def("sparse_table_ptr", &PyKVServer::SparseTablePtr)
@@ -1160,6 +1175,26 @@ PYBIND11_MODULE(_core, m) {
         py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
         py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
         py::arg("grid_cap") = 0);
+  // one lazy Adam step over the rows (kernels.h); out = 0: no gather. lr or
+  // eps <= 0, a beta outside [0, 1) or a state off a 16 B boundary raises
+  // ValueError before any GPU call.
+  m.def("k_sparse_lazy_adam_f32",
+        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+           uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
+           bool rowwise, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseLazyAdamF32(reinterpret_cast<float*>(table), reinterpret_cast<float*>(state),
+                                  reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                  reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out), lr,
+                                  beta1, beta2, eps, rowwise, nullptr, key_shift, row_base,
+                                  table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("rowwise"), py::arg("key_shift") = 0, py::arg("row_base") = 0,
+        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("sparse_lazy_adam_state_floats", &kern::SparseLazyAdamStateFloats, py::arg("rows"),
+        py::arg("row_len"), py::arg("rowwise"));
   // ids -> sorted unique keys, summed rows, slot per occurrence (kernels.h);
   // returns the number of unique keys. grad = 0: no gradients, sums = 0: no
   // sums. A bad argument raises ValueError before any GPU call.

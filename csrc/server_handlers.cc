@@ -759,7 +759,12 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
 }
 
 void GpuSparseHandler::ResetState() {
-  std::vector<float> host(state_floats(), opt_.init_acc);
+  std::vector<float> host(state_floats(), lazy_adam() ? 0.f : opt_.init_acc);
+  if (lazy_adam()) {
+    // a fresh record: the running products p1 = p2 = 1, everything else +0.0
+    size_t rec = kern::SparseLazyAdamStateFloats(1, row_len_, rowwise());
+    for (size_t r = 0; r < rows_; ++r) host[r * rec] = host[r * rec + 1] = 1.f;
+  }
   XPS_HIP_CHECK(hipMemcpy(state_.data(), host.data(), host.size() * sizeof(float),
                           hipMemcpyHostToDevice));
 }
@@ -833,9 +838,16 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     if (req.pull) out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
     OrderAfter(stream);
     float* out_rows = req.pull ? reinterpret_cast<float*>(out.data()) : nullptr;
-    kern::SparseAdagradF32(table, reinterpret_cast<float*>(state_.data()), rows, n, row_len_,
-                           kvs.vals.data(), out_rows, lr_.load(std::memory_order_relaxed),
-                           opt_.eps, rowwise(), stream, key_shift_, row_base_, rows_);
+    float* state = reinterpret_cast<float*>(state_.data());
+    float lr = lr_.load(std::memory_order_relaxed);
+    if (lazy_adam()) {
+      kern::SparseLazyAdamF32(table, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
+                              opt_.beta1, opt_.beta2, opt_.eps, rowwise(), stream, key_shift_,
+                              row_base_, rows_);
+    } else {
+      kern::SparseAdagradF32(table, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
+                             opt_.eps, rowwise(), stream, key_shift_, row_base_, rows_);
+    }
     Publish(stream);
     if (req.pull) {
       RespondRows(req, out, n, stream, server);

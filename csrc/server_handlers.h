@@ -170,16 +170,18 @@ class GpuDenseHandler {
 //
 // With an optimizer the handler keeps the optimizer state beside the table
 // and the push's cmd names the operation: kCmdDefault = one gradient step
-// (kern::SparseAdagradF32; state updated), kCmdAssign = assign rows (how
-// weights are initialised; state untouched), kCmdSum = add (state
-// untouched). `accumulate` plays no part then.
-enum class SparseOpt { kNone, kAdagrad, kRowwiseAdagrad };
+// (kern::SparseAdagradF32 or kern::SparseLazyAdamF32; state updated),
+// kCmdAssign = assign rows (how weights are initialised; state untouched),
+// kCmdSum = add (state untouched). `accumulate` plays no part then.
+enum class SparseOpt { kNone, kAdagrad, kRowwiseAdagrad, kLazyAdam, kRowwiseLazyAdam };
 
 struct SparseOptConfig {
   SparseOpt kind = SparseOpt::kNone;
   float lr = 0.01f;
   float eps = 1e-8f;
-  float init_acc = 0.f;  // the state's value before the first step
+  float init_acc = 0.f;  // Adagrad: the state's value before the first step
+  float beta1 = 0.9f;    // lazy Adam: decay of the first moment
+  float beta2 = 0.999f;  // lazy Adam: decay of the second moment
 };
 
 class GpuSparseHandler {
@@ -192,13 +194,14 @@ class GpuSparseHandler {
                    int key_shift = 0, SparseOptConfig opt = SparseOptConfig());
   void operator()(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   uintptr_t table_ptr() const { return reinterpret_cast<uintptr_t>(table_.data()); }
-  // the optimizer state (rows floats row-wise, else the table's shape); 0 without one
+  // the optimizer state; 0 without one. Adagrad: rows floats row-wise, else
+  // the table's shape. Lazy Adam: kern::SparseLazyAdamF32's records.
   uintptr_t state_ptr() const { return reinterpret_cast<uintptr_t>(state_.data()); }
   // learning rate of the gradient steps handled after the call
   void set_lr(float lr) { lr_.store(lr, std::memory_order_relaxed); }
   // Checkpoint: u64 rows, row_len, key_shift, then the table; with an
-  // optimizer u64 state_floats and the state follow. Loading a file that
-  // ends after the table resets the state to init_acc.
+  // optimizer u64 state_floats and the state, as it lies, follow. Loading
+  // a file that ends after the table resets the state to a fresh one.
   void Save(const std::string& path);
   void Load(const std::string& path);
 
@@ -215,9 +218,19 @@ class GpuSparseHandler {
   // the push of an optimizer handler; with req.pull it answers the pull too
   void OptimizerPush(const KVMeta& req, const KVPairs<float>& kvs, const uint64_t* rows,
                      hipStream_t stream, KVServer<float>* server);
-  bool rowwise() const { return opt_.kind == SparseOpt::kRowwiseAdagrad; }
-  size_t state_floats() const { return rowwise() ? rows_ : rows_ * row_len_; }
-  void ResetState();  // state = init_acc, synchronously
+  bool rowwise() const {
+    return opt_.kind == SparseOpt::kRowwiseAdagrad || opt_.kind == SparseOpt::kRowwiseLazyAdam;
+  }
+  bool lazy_adam() const {
+    return opt_.kind == SparseOpt::kLazyAdam || opt_.kind == SparseOpt::kRowwiseLazyAdam;
+  }
+  size_t state_floats() const {
+    if (lazy_adam()) return kern::SparseLazyAdamStateFloats(rows_, row_len_, rowwise());
+    return rowwise() ? rows_ : rows_ * row_len_;
+  }
+  // the state before any step, synchronously: init_acc (Adagrad), or
+  // records of p1 = p2 = 1 and zeros (lazy Adam)
+  void ResetState();
   // chain_: every kernel that touches the table waits for the one before
   // it (OrderAfter) and leaves its event for the next (Publish)
   void OrderAfter(hipStream_t s);

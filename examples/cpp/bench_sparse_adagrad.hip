@@ -3,7 +3,7 @@
 // scatter-add and the gather of csrc/kernels.hip, on the same buffers.
 // Links kernels.hip and sparse_opt.hip only: no cluster, no Python.
 //
-//   build/bench_sparse_adagrad [--rounds N]
+//   build/bench_sparse_adagrad [--rounds N] [--opt lazy_adam|rowwise_lazy_adam]
 //
 // Shape: the sparse bench config, a 1M x 64 fp32 table with 8192 unique
 // rows per step. Two key schedules: "hot", the same 8192 rows every step
@@ -13,6 +13,9 @@
 // HIP events and in alternation:
 //   fused   SparseAdagradF32, row-wise, with out  (one launch)
 //   pair    SparseScatterAddF32 + SparseGatherF32 (two launches)
+// With --opt the rounds time instead, in the same alternation:
+//   adam    SparseLazyAdamF32 of that variant, with out (one launch)
+//   adagrad SparseAdagradF32, row-wise, with out        (one launch)
 // Output: median, 10th and 90th percentile of each in microseconds.
 #include <hip/hip_runtime.h>
 
@@ -47,6 +50,13 @@ __global__ void fill_kernel(float* p, size_t n, unsigned salt, float scale) {
   }
 }
 
+// fresh lazy-Adam records of rec floats: p1 = p2 = 1, the rest +0.0
+__global__ void fresh_kernel(float* p, size_t n, size_t rec) {
+  size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < n; i += stride) p[i] = i % rec < 2 ? 1.f : 0.f;
+}
+
 void Report(const char* schedule, const char* name, std::vector<float>* us) {
   std::sort(us->begin(), us->end());
   size_t n = us->size();
@@ -54,15 +64,66 @@ void Report(const char* schedule, const char* name, std::vector<float>* us) {
          (*us)[n * 9 / 10]);
 }
 
+// microseconds of the launches fn() makes, between two events on the null stream
+template <class Fn>
+float TimeUs(hipEvent_t e0, hipEvent_t e1, Fn fn) {
+  float ms = 0;
+  CHECK(hipEventRecord(e0, nullptr));
+  fn();
+  CHECK(hipEventRecord(e1, nullptr));
+  CHECK(hipEventSynchronize(e1));
+  CHECK(hipEventElapsedTime(&ms, e0, e1));
+  return ms * 1000.f;
+}
+
+// --opt: the lazy-Adam launch against the row-wise Adagrad launch, both with
+// out, on the same table, gradients and keys; Adagrad visits the set half a
+// turn away, as the pair does in the default mode
+void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* grad, float* out,
+                const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
+  size_t nstate = xps::kern::SparseLazyAdamStateFloats(kRows, kRowLen, rowwise);
+  float* records;
+  CHECK(hipMalloc(reinterpret_cast<void**>(&records), nstate * 4));
+  hipLaunchKernelGGL(fresh_kernel, dim3(4096), dim3(256), 0, nullptr, records, nstate,
+                     nstate / kRows);
+  CHECK(hipDeviceSynchronize());
+  for (int rotating = 0; rotating < 2; ++rotating) {
+    std::vector<float> us_adam, us_adagrad;
+    for (int r = -20; r < rounds; ++r) {
+      size_t turn = static_cast<size_t>(r + 20);
+      const uint64_t* k = keys + (rotating ? (turn % kSets) * kHot : 0);
+      float us = TimeUs(e0, e1, [&] {
+        xps::kern::SparseLazyAdamF32(table, records, k, kHot, kRowLen, grad, out, 0.01f, 0.9f,
+                                     0.999f, 1e-8f, rowwise, nullptr, 0, 0, kRows);
+      });
+      if (r >= 0) us_adam.push_back(us);
+      if (rotating) k = keys + ((turn + kSets / 2) % kSets) * kHot;
+      us = TimeUs(e0, e1, [&] {
+        xps::kern::SparseAdagradF32(table, state, k, kHot, kRowLen, grad, out, 0.01f, 1e-8f,
+                                    /*rowwise=*/true, nullptr, 0, 0, kRows);
+      });
+      if (r >= 0) us_adagrad.push_back(us);
+    }
+    CHECK(hipGetLastError());
+    Report(rotating ? "rotating" : "hot", "adam", &us_adam);
+    Report(rotating ? "rotating" : "hot", "adagrad", &us_adagrad);
+  }
+  CHECK(hipFree(records));
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   int rounds = 500;
+  const char* opt = nullptr;  // none: the default comparison
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--rounds") && i + 1 < argc) {
       rounds = atoi(argv[++i]);
+    } else if (!strcmp(argv[i], "--opt") && i + 1 < argc &&
+               (!strcmp(argv[i + 1], "lazy_adam") || !strcmp(argv[i + 1], "rowwise_lazy_adam"))) {
+      opt = argv[++i];
     } else {
-      fprintf(stderr, "usage: %s [--rounds N]\n", argv[0]);
+      fprintf(stderr, "usage: %s [--rounds N] [--opt lazy_adam|rowwise_lazy_adam]\n", argv[0]);
       return 2;
     }
   }
@@ -92,6 +153,10 @@ int main(int argc, char** argv) {
   printf("# %zu x %zu table, %zu rows per step, %d rounds, microseconds\n", kRows, kRowLen, kHot,
          rounds);
   printf("%-9s %-6s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
+  if (opt) {
+    AdamRounds(!strcmp(opt, "rowwise_lazy_adam"), rounds, table, state, grad, out, keys, e0, e1);
+    return 0;
+  }
   for (int rotating = 0; rotating < 2; ++rotating) {
     std::vector<float> us_fused, us_pair;
     for (int r = -20; r < rounds; ++r) {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Embedding-bag regression with the optimizer on the server: the table
-lives in the sparse handler, row-wise Adagrad runs there, and a training
-step is ONE fused zpushpull_ptr.
+lives in the sparse handler, the optimizer step (row-wise Adagrad unless
+--optimizer names another) runs there, and a training step is ONE fused
+zpushpull_ptr.
 
 Each sample is a bag of row ids whose embeddings are summed and regressed
 onto the sum of a hidden table's rows. A step's message carries the
@@ -15,7 +16,9 @@ every occurrence, and one sparse_gather turns the response back into
 per-occurrence rows.
 
 Needs one MI355X.  Run:  python examples/python/train_embedding.py
+                        [--optimizer rowwise_adagrad|adagrad|lazy_adam|rowwise_lazy_adam]
 """
+import argparse
 import sys
 import threading
 
@@ -26,18 +29,24 @@ import ps_lite_amd as ps  # noqa: E402
 from ps_lite_amd import ops  # noqa: E402
 
 ROWS, DIM, BATCH, BAG, STEPS = 512, 32, 256, 4, 60
+# learning rates at which the loss falls well within STEPS: Adam's step is
+# about lr per element whatever the gradient's scale
+LR = {"adagrad": 0.1, "rowwise_adagrad": 0.1, "lazy_adam": 0.05, "rowwise_lazy_adam": 0.05}
 
 
 def main():
     import torch
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--optimizer", default="rowwise_adagrad", choices=sorted(LR))
+    optimizer = ap.parse_args().optimizer
     ps.setup_env(1, 1, root_port=9310, XPS_DEV_ID=0, XPS_POOL_GB=1)
     roles = (("scheduler", -1), ("joint", 0))
     ths = [threading.Thread(target=ps.start, kwargs=dict(role=r, device=d)) for r, d in roles]
     [t.start() for t in ths]
     [t.join() for t in ths]
     server = ps.KVServer(0)
-    server.set_gpu_sparse_handle(ROWS, DIM, optimizer="rowwise_adagrad", lr=0.1, eps=1e-8)
+    server.set_gpu_sparse_handle(ROWS, DIM, optimizer=optimizer, lr=LR[optimizer], eps=1e-8)
     worker = ps.KVWorker(0, 0)
 
     gen = torch.Generator().manual_seed(3)
@@ -85,7 +94,7 @@ def main():
     [t.start() for t in ths]
     [t.join() for t in ths]
     assert losses[-1] < 0.5 * losses[0], "the loss did not fall"
-    print("loss %.4f -> %.4f with row-wise Adagrad on the server" % (losses[0], losses[-1]))
+    print("loss %.4f -> %.4f with %s on the server" % (losses[0], losses[-1], optimizer))
 
 
 if __name__ == "__main__":

@@ -2,4 +2,4 @@ from .dense import dense_assign, dense_sum  # noqa: F401
 from .mx import (mxfp8_dequantize, mxfp8_dequantize_many, mxfp8_packed_nbytes,  # noqa: F401
                  mxfp8_quantize, mxfp8_quantize_many)
 from .sparse import (sparse_adagrad, sparse_coalesce, sparse_gather,  # noqa: F401
-                     sparse_scatter_add)
+                     sparse_lazy_adam, sparse_lazy_adam_state, sparse_scatter_add)

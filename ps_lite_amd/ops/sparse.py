@@ -85,3 +85,41 @@ def sparse_adagrad(table, state, rows, grad, lr, eps=1e-8, out=None):
                                0 if out is None else out.data_ptr(), lr, eps, rowwise,
                                table_rows=table.shape[0])
     return table if out is None else out
+
+
+def sparse_lazy_adam_state(table, rowwise=False):
+    """A fresh lazy-Adam state for `table`: a flat fp32 tensor of one record
+    per row, {p1, p2, v_row, 0} m[row_len] and, element-wise only, v[row_len],
+    with p1 = p2 = 1 and zeros everywhere else."""
+    import torch
+
+    rows, row_len = table.shape
+    state = torch.zeros(_core.sparse_lazy_adam_state_floats(rows, row_len, rowwise),
+                        device=table.device, dtype=torch.float32)
+    state.view(rows, -1)[:, :2] = 1.0
+    return state
+
+
+def sparse_lazy_adam(table, state, rows, grad, lr, beta1=0.9, beta2=0.999, eps=1e-8,
+                     rowwise=False, out=None):
+    """One sparse Adam step on table[rows[i]] with gradient grad[i], in one launch.
+
+    The bias correction is each row's own: its record in `state`
+    (sparse_lazy_adam_state) carries p1 = beta1^t and p2 = beta2^t over the
+    steps that row has taken. m = beta1 * m + (1 - beta1) * g; v = beta2 * v +
+    (1 - beta2) * g * g per element, or with rowwise one v per row from
+    mean(g * g); then table[row] -= lr / (1 - p1) * m / (sqrt(v / (1 - p2)) +
+    eps). Rows must be unique; a row outside the table is skipped. With `out`
+    the new rows are also written to out[i] (zeros for a skipped row).
+    Returns out, or table without one."""
+    assert table.is_cuda and table.dim() == 2 and table.is_contiguous()
+    assert state.is_cuda and state.dim() == 1 and state.is_contiguous()
+    assert state.numel() == _core.sparse_lazy_adam_state_floats(*table.shape, rowwise)
+    assert rows.is_cuda and rows.dim() == 1
+    assert grad.is_contiguous() and grad.shape == (rows.numel(), table.shape[1])
+    assert out is None or (out.is_contiguous() and out.shape == grad.shape)
+    _core.k_sparse_lazy_adam_f32(table.data_ptr(), state.data_ptr(), rows.data_ptr(),
+                                 rows.numel(), table.shape[1], grad.data_ptr(),
+                                 0 if out is None else out.data_ptr(), lr, beta1, beta2, eps,
+                                 rowwise, table_rows=table.shape[0])
+    return table if out is None else out
