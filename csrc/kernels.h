@@ -104,6 +104,55 @@ void SparseLazyAdamF32(float* table, float* state, const uint64_t* rows_dev, siz
                        size_t row_len, const float* grad, float* out_or_null, float lr, float beta1,
                        float beta2, float eps, bool rowwise, hipStream_t s, int key_shift = 0,
                        uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
+// The same ops over a bf16 table (sparse_bf16.hip): `table` holds bf16 bits,
+// every other array stays fp32. A weight is widened exactly, the fp32
+// operations are those of the F32 sibling in the same order, and the result
+// x (bits u) is rounded once on the store by R:
+//   kNearest:    round-to-nearest-even
+//   kStochastic: (u + r) >> 16, r uniform in [0, 2^16): the magnitude goes up
+//                with probability (u & 0xffff) / 2^16; a bf16 value keeps its bits
+// Inf and NaN pass through both. r is 16 bits of a counter-based generator
+// keyed on (seed, local row, element index) (SplitMix64, stated at the top
+// of sparse_bf16.hip): the same call gives the same table bits under any
+// grid_cap and on either path. Rows move as 8-element units (one 16 B table
+// access against two float4) when row_len % 8 == 0 and the table and the
+// fp32 arrays (an element-wise Adagrad state included) are 16 B-aligned,
+// else element by element for the whole call.
+enum class Bf16Rounding { kNearest, kStochastic };
+// the seed of a handler's n-th rounding launch: mix(seed + (n + 1) * phi)
+uint64_t SparseBf16LaunchSeed(uint64_t seed, uint64_t n);
+// out[r][:] = float(table[row(r)][:]), exact; zeros for a key outside the table
+void SparseGatherBf16(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                      size_t row_len, float* out, hipStream_t s, int key_shift = 0,
+                      uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
+// table[row(r)][:] = RNE_bf16(src[r][:]): always nearest, no seed (how
+// weights are initialised)
+void SparseScatterAssignBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                             size_t row_len, const float* src, hipStream_t s, int key_shift = 0,
+                             uint64_t row_base = 0, uint64_t table_rows = ~0ull,
+                             int grid_cap = 0);
+// table[row(r)][:] = R(float(table[row(r)][:]) + src[r][:]), one fp32 add.
+// Not atomic: in-range rows of one call must be unique, and calls on one
+// table ordered by the caller.
+void SparseScatterAddBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
+                          const float* src, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
+                          int key_shift = 0, uint64_t row_base = 0, uint64_t table_rows = ~0ull,
+                          int grid_cap = 0);
+// SparseAdagradF32 / SparseLazyAdamF32 with table[row][c] = R(w'): the same
+// state layouts, records, requirements and std::invalid_argument cases. With
+// out_or_null set, out[r][c] is the stored bf16 widened, what a later gather
+// returns bit for bit (not the unrounded w'), or zeros for a row outside the
+// table.
+void SparseAdagradBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                       size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
+                       bool rowwise, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
+                       int key_shift = 0, uint64_t row_base = 0, uint64_t table_rows = ~0ull,
+                       int grid_cap = 0);
+void SparseLazyAdamBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                        size_t row_len, const float* grad, float* out_or_null, float lr,
+                        float beta1, float beta2, float eps, bool rowwise, Bf16Rounding rounding,
+                        uint64_t seed, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
+                        uint64_t table_rows = ~0ull, int grid_cap = 0);
 // Worker side of the sparse ops (sparse_coalesce.hip): a batch's ids, in any
 // order and with any repetition, become the sorted unique keys the ops above
 // and the handlers want. ids compare as unsigned 64-bit values.

@@ -28,6 +28,13 @@ using namespace xps;
 
 namespace {
 
+// the store rule of a bf16 table by name; ValueError for any other
+kern::Bf16Rounding ParseRounding(const std::string& name) {
+  if (name == "stochastic") return kern::Bf16Rounding::kStochastic;
+  if (name == "nearest") return kern::Bf16Rounding::kNearest;
+  throw py::value_error("rounding must be \"stochastic\" or \"nearest\" (got \"" + name + "\")");
+}
+
 struct PoolBuffer {
   SArray<char> arr;
   uintptr_t ptr() const { return reinterpret_cast<uintptr_t>(arr.data()); }
@@ -331,12 +338,28 @@ class PyKVServer {
 
   // optimizer: None, "adagrad", "rowwise_adagrad", "lazy_adam" or
   // "rowwise_lazy_adam" (the sparse Adam with per-row bias correction; there
-  // is no dense "adam"). Bad arguments raise ValueError before the handler
+  // is no dense "adam"). table_dtype "f32" or "bf16"; a bf16 table needs an
+  // optimizer and takes rounding ("stochastic" or "nearest") and seed, which
+  // an fp32 table refuses. Bad arguments raise ValueError before the handler
   // (and with it the GPU) is touched.
   void SetGpuSparseHandle(size_t rows, size_t row_len, bool accumulate, int key_shift,
                           py::object optimizer, float lr, float eps, float init_acc, float beta1,
-                          float beta2) {
+                          float beta2, const std::string& table_dtype,
+                          const std::string& rounding, uint64_t seed) {
     SparseOptConfig opt;
+    if (table_dtype == "bf16") {
+      opt.table_dtype = SparseTableDtype::kBf16;
+    } else if (table_dtype != "f32") {
+      throw py::value_error("table_dtype must be \"f32\" or \"bf16\" (got \"" + table_dtype +
+                            "\")");
+    }
+    opt.rounding = ParseRounding(rounding);
+    opt.seed = seed;
+    if (opt.table_dtype == SparseTableDtype::kBf16) {
+      if (optimizer.is_none()) throw py::value_error("a bf16 table needs an optimizer");
+    } else if (rounding != "stochastic" || seed != 0) {
+      throw py::value_error("rounding and seed belong to a bf16 table: an fp32 table has none");
+    }
     if (!optimizer.is_none()) {
       std::string name = py::cast<std::string>(optimizer);
       if (name == "adagrad") {
@@ -611,7 +634,9 @@ PYBIND11_MODULE(_core, m) {
       .def("set_gpu_sparse_handle", &PyKVServer::SetGpuSparseHandle, py::arg("rows"),
            py::arg("row_len"), py::arg("accumulate") = true, py::arg("key_shift") = 0,
            py::arg("optimizer") = py::none(), py::arg("lr") = 0.01f, py::arg("eps") = 1e-8f,
-           py::arg("init_acc") = 0.0f, py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f)
+           py::arg("init_acc") = 0.0f, py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f,
+           py::arg("table_dtype") = "f32", py::arg("rounding") = "stochastic",
+           py::arg("seed") = 0)
       .def("register_entry", &PyKVServer::RegisterEntry, py::arg("key"), py::arg("ptr"),
            py::arg("nbytes"), py::arg("device") = 0)
       .def("sparse_table_ptr", &PyKVServer::SparseTablePtr)
@@ -1195,6 +1220,81 @@ PYBIND11_MODULE(_core, m) {
         py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
   m.def("sparse_lazy_adam_state_floats", &kern::SparseLazyAdamStateFloats, py::arg("rows"),
         py::arg("row_len"), py::arg("rowwise"));
+  // the same ops over a bf16 table (kernels.h): table holds bf16 bits, the
+  // rest stays fp32; rounding "stochastic" or "nearest", anything else raises
+  // ValueError before any GPU call, like the siblings' argument checks
+  m.def("k_sparse_gather_bf16",
+        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
+           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseGatherBf16(reinterpret_cast<uint16_t*>(table),
+                                 reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                 reinterpret_cast<float*>(out), nullptr, key_shift, row_base,
+                                 table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
+  m.def("k_sparse_scatter_assign_bf16",
+        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
+           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseScatterAssignBf16(reinterpret_cast<uint16_t*>(table),
+                                        reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                        reinterpret_cast<float*>(src), nullptr, key_shift,
+                                        row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
+  m.def("k_sparse_scatter_add_bf16",
+        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
+           const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
+           uint64_t table_rows, int grid_cap) {
+          kern::SparseScatterAddBf16(reinterpret_cast<uint16_t*>(table),
+                                     reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                     reinterpret_cast<float*>(src), ParseRounding(rounding), seed,
+                                     nullptr, key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
+        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("k_sparse_adagrad_bf16",
+        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+           uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise,
+           const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
+           uint64_t table_rows, int grid_cap) {
+          kern::SparseAdagradBf16(reinterpret_cast<uint16_t*>(table),
+                                  reinterpret_cast<float*>(state),
+                                  reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                  reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out),
+                                  lr, eps, rowwise, ParseRounding(rounding), seed, nullptr,
+                                  key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
+        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
+        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("k_sparse_lazy_adam_bf16",
+        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+           uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
+           bool rowwise, const std::string& rounding, uint64_t seed, int key_shift,
+           uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseLazyAdamBf16(reinterpret_cast<uint16_t*>(table),
+                                   reinterpret_cast<float*>(state),
+                                   reinterpret_cast<uint64_t*>(rows), nrows, row_len,
+                                   reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out),
+                                   lr, beta1, beta2, eps, rowwise, ParseRounding(rounding), seed,
+                                   nullptr, key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("rowwise"), py::arg("rounding") = "stochastic",
+        py::arg("seed") = 0, py::arg("key_shift") = 0, py::arg("row_base") = 0,
+        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
   // ids -> sorted unique keys, summed rows, slot per occurrence (kernels.h);
   // returns the number of unique keys. grad = 0: no gradients, sums = 0: no
   // sums. A bad argument raises ValueError before any GPU call.

@@ -749,8 +749,9 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
     uint64_t low = (1ull << key_shift_) - 1;
     row_base_ = (begin >> key_shift_) + ((begin & low) ? 1 : 0);
   }
+  XPS_CHECK(!bf16() || has_opt) << "a bf16 sparse table needs an optimizer";
   XPS_HIP_CHECK(hipSetDevice(pool->device()));
-  table_ = pool->AllocArray(rows * row_len * sizeof(float));
+  table_ = pool->AllocArray(rows * row_len * (bf16() ? sizeof(uint16_t) : sizeof(float)));
   XPS_HIP_CHECK(hipMemset(table_.data(), 0, table_.size()));
   if (has_opt) {
     state_ = pool->AllocArray(state_floats() * sizeof(float));
@@ -818,8 +819,15 @@ void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, si
                                      hipStream_t stream, KVServer<float>* server) {
   SArray<char> out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
   OrderAfter(stream);
-  kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
-                        reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_, rows_);
+  if (bf16()) {
+    kern::SparseGatherBf16(reinterpret_cast<const uint16_t*>(table_.data()), rows, n, row_len_,
+                           reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_,
+                           rows_);
+  } else {
+    kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
+                          reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_,
+                          rows_);
+  }
   Publish(stream);
   RespondRows(req, out, n, stream, server);
 }
@@ -829,6 +837,7 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
                                      KVServer<float>* server) {
   size_t n = kvs.keys.size();
   float* table = reinterpret_cast<float*>(table_.data());
+  uint16_t* table16 = reinterpret_cast<uint16_t*>(table_.data());
   XPS_CHECK(req.cmd == kCmdDefault || req.cmd == kCmdAssign || req.cmd == kCmdSum)
       << "optimizer sparse handler: cmd " << req.cmd << " names no operation";
   if (req.cmd == kCmdDefault) {
@@ -840,7 +849,15 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     float* out_rows = req.pull ? reinterpret_cast<float*>(out.data()) : nullptr;
     float* state = reinterpret_cast<float*>(state_.data());
     float lr = lr_.load(std::memory_order_relaxed);
-    if (lazy_adam()) {
+    if (bf16() && lazy_adam()) {
+      kern::SparseLazyAdamBf16(table16, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
+                               opt_.beta1, opt_.beta2, opt_.eps, rowwise(), opt_.rounding,
+                               NextSeed(), stream, key_shift_, row_base_, rows_);
+    } else if (bf16()) {
+      kern::SparseAdagradBf16(table16, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
+                              opt_.eps, rowwise(), opt_.rounding, NextSeed(), stream, key_shift_,
+                              row_base_, rows_);
+    } else if (lazy_adam()) {
       kern::SparseLazyAdamF32(table, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
                               opt_.beta1, opt_.beta2, opt_.eps, rowwise(), stream, key_shift_,
                               row_base_, rows_);
@@ -855,7 +872,13 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     }
   } else {
     OrderAfter(stream);
-    if (req.cmd == kCmdSum) {
+    if (bf16() && req.cmd == kCmdSum) {
+      kern::SparseScatterAddBf16(table16, rows, n, row_len_, kvs.vals.data(), opt_.rounding,
+                                 NextSeed(), stream, key_shift_, row_base_, rows_);
+    } else if (bf16()) {
+      kern::SparseScatterAssignBf16(table16, rows, n, row_len_, kvs.vals.data(), stream,
+                                    key_shift_, row_base_, rows_);
+    } else if (req.cmd == kCmdSum) {
       kern::SparseScatterAddF32(table, rows, n, row_len_, kvs.vals.data(), /*atomic=*/false, stream,
                                 key_shift_, row_base_, rows_);
     } else {
@@ -907,10 +930,14 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
   }
 }
 
+// bit 32 of the checkpoint's third header word: the table holds bf16
+static constexpr uint64_t kCkptBf16 = 1ull << 32;
+
 void GpuSparseHandler::Save(const std::string& path) {
   FILE* f = fopen(path.c_str(), "wb");
   XPS_CHECK(f) << "cannot open checkpoint " << path;
-  uint64_t hdr[3] = {rows_, row_len_, static_cast<uint64_t>(key_shift_)};
+  uint64_t hdr[3] = {rows_, row_len_,
+                     static_cast<uint32_t>(key_shift_) | (bf16() ? kCkptBf16 : 0)};
   fwrite(hdr, 8, 3, f);
   std::vector<char> host(table_.size());
   XPS_HIP_CHECK(hipMemcpy(host.data(), table_.data(), table_.size(), hipMemcpyDeviceToHost));
@@ -921,6 +948,10 @@ void GpuSparseHandler::Save(const std::string& path) {
     host.resize(state_.size());
     XPS_HIP_CHECK(hipMemcpy(host.data(), state_.data(), state_.size(), hipMemcpyDeviceToHost));
     fwrite(host.data(), 1, host.size(), f);
+    if (bf16()) {
+      uint64_t launches = launches_.load();
+      fwrite(&launches, 8, 1, f);
+    }
   }
   fclose(f);
 }
@@ -932,6 +963,7 @@ void GpuSparseHandler::Load(const std::string& path) {
   XPS_CHECK_EQ(fread(hdr, 8, 3, f), 3u);
   XPS_CHECK_EQ(hdr[0], rows_);
   XPS_CHECK_EQ(hdr[1], row_len_);
+  XPS_CHECK_EQ((hdr[2] & kCkptBf16) != 0, bf16()) << "checkpoint of another table dtype";
   std::vector<char> host(table_.size());
   XPS_CHECK_EQ(fread(host.data(), 1, host.size(), f), host.size());
   XPS_HIP_CHECK(hipMemcpy(table_.data(), host.data(), table_.size(), hipMemcpyHostToDevice));
@@ -945,6 +977,9 @@ void GpuSparseHandler::Load(const std::string& path) {
     } else {
       ResetState();  // a file that ends after the table: a fresh optimizer
     }
+    uint64_t launches = 0;
+    if (bf16() && fread(&launches, 8, 1, f) != 1) launches = 0;  // an older file
+    launches_.store(launches);
   }
   fclose(f);
 }

@@ -173,7 +173,17 @@ class GpuDenseHandler {
 // (kern::SparseAdagradF32 or kern::SparseLazyAdamF32; state updated),
 // kCmdAssign = assign rows (how weights are initialised; state untouched),
 // kCmdSum = add (state untouched). `accumulate` plays no part then.
+//
+// A bf16 table (SparseTableDtype::kBf16; needs an optimizer) holds
+// rows * row_len * 2 bytes and goes through kern::Sparse*Bf16. The wire does
+// not change: pushes and pull responses stay fp32, lens count floats. The
+// n-th launch that rounds (a step or an add; n counts from 0 and is
+// checkpointed) gets kern::SparseBf16LaunchSeed(seed, n), so a replayed
+// message sequence reproduces the table bit for bit. Without an optimizer
+// concurrent workers would need a 16-bit atomic add, which does not exist;
+// the optimizer handler orders whole kernels instead (chain_).
 enum class SparseOpt { kNone, kAdagrad, kRowwiseAdagrad, kLazyAdam, kRowwiseLazyAdam };
+enum class SparseTableDtype { kF32, kBf16 };
 
 struct SparseOptConfig {
   SparseOpt kind = SparseOpt::kNone;
@@ -182,11 +192,15 @@ struct SparseOptConfig {
   float init_acc = 0.f;  // Adagrad: the state's value before the first step
   float beta1 = 0.9f;    // lazy Adam: decay of the first moment
   float beta2 = 0.999f;  // lazy Adam: decay of the second moment
+  SparseTableDtype table_dtype = SparseTableDtype::kF32;
+  kern::Bf16Rounding rounding = kern::Bf16Rounding::kStochastic;  // bf16 table: the store rule
+  uint64_t seed = 0;                                              // bf16 table, stochastic
 };
 
 class GpuSparseHandler {
  public:
-  // Allocates (and zeroes) a rows x row_len fp32 table shard in the pool.
+  // Allocates (and zeroes) a rows x row_len table shard in the pool, fp32 or
+  // (opt.table_dtype) bf16.
   // key_shift: workers send key = global_row << key_shift so the key-range
   // slicer shards rows evenly; this server's local row =
   // (key >> key_shift) - row_base, row_base derived from its key range.
@@ -199,9 +213,12 @@ class GpuSparseHandler {
   uintptr_t state_ptr() const { return reinterpret_cast<uintptr_t>(state_.data()); }
   // learning rate of the gradient steps handled after the call
   void set_lr(float lr) { lr_.store(lr, std::memory_order_relaxed); }
-  // Checkpoint: u64 rows, row_len, key_shift, then the table; with an
-  // optimizer u64 state_floats and the state, as it lies, follow. Loading
-  // a file that ends after the table resets the state to a fresh one.
+  // Checkpoint: u64 rows, row_len, and a word of key_shift (low 32 bits) and
+  // the table dtype (bit 32: bf16), then the table as it lies; with an
+  // optimizer u64 state_floats and the state, as it lies, follow, and after
+  // them on a bf16 table the u64 launch counter. Loading a file that ends
+  // after the table resets the state to a fresh one, one that ends before
+  // the counter sets it to 0; the file's dtype must be the handler's.
   void Save(const std::string& path);
   void Load(const std::string& path);
 
@@ -235,6 +252,9 @@ class GpuSparseHandler {
   // it (OrderAfter) and leaves its event for the next (Publish)
   void OrderAfter(hipStream_t s);
   void Publish(hipStream_t s);
+  bool bf16() const { return opt_.table_dtype == SparseTableDtype::kBf16; }
+  // the seed of the next launch that rounds; counts it
+  uint64_t NextSeed() { return kern::SparseBf16LaunchSeed(opt_.seed, launches_.fetch_add(1)); }
 
   Postoffice* po_;
   size_t rows_;
@@ -247,6 +267,7 @@ class GpuSparseHandler {
   SparseOptConfig opt_;
   std::atomic<float> lr_{0.f};
   SArray<char> state_;
+  std::atomic<uint64_t> launches_{0};  // bf16 table: launches that rounded so far
   // optimizer with > 1 workers: a step is a read-modify-write that atomics
   // cannot make safe, and the workers' messages run on different peer
   // streams, so one event orders every kernel on the table (the dense

@@ -41,6 +41,7 @@
 #include <stdexcept>
 
 #include "kernels.h"
+#include "sparse_elem.h"
 
 namespace xps {
 namespace kern {
@@ -52,14 +53,8 @@ constexpr int kKeep = 4;  // gradient vectors a lane keeps between the two passe
 __device__ inline float SumSq(float v) { return v * v; }
 __device__ inline float SumSq(float4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
 
-// IEEE multiply, square root, add, divide and subtract, in that order:
-// the tests' error bound counts one rounding for each
-__device__ inline float Step(float w, float g, float lr, float denom) {
-  return w - (lr * g) / denom;
-}
-__device__ inline float Denom(float s, float eps) { return sqrtf(s) + eps; }
-
-// new weights of one vector given a ready denominator (row-wise)
+// new weights of one vector given a ready denominator (row-wise); Step,
+// Denom and the lazy-Adam rules are sparse_elem.h's
 __device__ inline float Update(float w, float g, float lr, float denom) {
   return Step(w, g, lr, denom);
 }
@@ -221,15 +216,6 @@ struct LazyAdamArgs {
   uint64_t tab_rows;
 };
 
-// beta * old + omb * x: both moments, the row-wise second one included
-__device__ inline float Moment(float old, float x, float beta, float omb) {
-  return beta * old + omb * x;
-}
-__device__ inline float AdamDenom(float v, float c2, float eps) { return sqrtf(v / c2) + eps; }
-__device__ inline float AdamStep(float w, float m, float alpha, float denom) {
-  return w - (alpha * m) / denom;
-}
-
 // One element's update. q is the row's denominator (row-wise; *v unused) or
 // its divisor c2 (element-wise).
 template <bool kRowwise>
@@ -250,26 +236,6 @@ __device__ inline void AdamElem(float4* w, float4* m, float4* v, float4 g, float
   AdamElem<kRowwise>(&w->y, &m->y, &v->y, g.y, alpha, q, a);
   AdamElem<kRowwise>(&w->z, &m->z, &v->z, g.z, alpha, q, a);
   AdamElem<kRowwise>(&w->w, &m->w, &v->w, g.w, alpha, q, a);
-}
-
-// a record's header {p1, p2, v_row, 0}: one 16 B access on the float4 path
-// (state base and record length are multiples of 16 B there), four floats
-// on the scalar path
-template <bool kVec>
-__device__ inline float4 LoadHeader(const float* rec) {
-  if (kVec) return *reinterpret_cast<const float4*>(rec);
-  return float4{rec[0], rec[1], rec[2], rec[3]};
-}
-template <bool kVec>
-__device__ inline void StoreHeader(float* rec, float4 h) {
-  if (kVec) {
-    *reinterpret_cast<float4*>(rec) = h;
-  } else {
-    rec[0] = h.x;
-    rec[1] = h.y;
-    rec[2] = h.z;
-    rec[3] = h.w;
-  }
 }
 
 template <class V, bool kRowwise>

@@ -1,9 +1,10 @@
 // One-process timing of the fused Adagrad step (csrc/sparse_opt.hip)
 // against the launches it replaces in a fused sparse round, the
 // scatter-add and the gather of csrc/kernels.hip, on the same buffers.
-// Links kernels.hip and sparse_opt.hip only: no cluster, no Python.
+// Links kernels.hip, sparse_opt.hip and sparse_bf16.hip only: no cluster, no
+// Python.
 //
-//   build/bench_sparse_adagrad [--rounds N] [--opt lazy_adam|rowwise_lazy_adam]
+//   build/bench_sparse_adagrad [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16]
 //
 // Shape: the sparse bench config, a 1M x 64 fp32 table with 8192 unique
 // rows per step. Two key schedules: "hot", the same 8192 rows every step
@@ -16,6 +17,12 @@
 // With --opt the rounds time instead, in the same alternation:
 //   adam    SparseLazyAdamF32 of that variant, with out (one launch)
 //   adagrad SparseAdagradF32, row-wise, with out        (one launch)
+// With --bf16 the rounds time three pairs, the bf16-table kernel
+// (sparse_bf16.hip, stochastic rounding) beside its fp32 sibling on the same
+// keys, gradients, state and out, the sibling's set half a turn away:
+//   adagrad / adagrad16   row-wise Adagrad step with out
+//   adam / adam16         row-wise lazy Adam step with out
+//   gather / gather16     SparseGatherF32 / SparseGatherBf16
 // Output: median, 10th and 90th percentile of each in microseconds.
 #include <hip/hip_runtime.h>
 
@@ -60,7 +67,7 @@ __global__ void fresh_kernel(float* p, size_t n, size_t rec) {
 void Report(const char* schedule, const char* name, std::vector<float>* us) {
   std::sort(us->begin(), us->end());
   size_t n = us->size();
-  printf("%-9s %-6s %9.2f %9.2f %9.2f\n", schedule, name, (*us)[n / 2], (*us)[n / 10],
+  printf("%-9s %-9s %9.2f %9.2f %9.2f\n", schedule, name, (*us)[n / 2], (*us)[n / 10],
          (*us)[n * 9 / 10]);
 }
 
@@ -111,19 +118,86 @@ void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* gra
   CHECK(hipFree(records));
 }
 
+// --bf16: each bf16-table kernel beside its fp32 sibling. Both tables see
+// the same keys; the two lazy-Adam launches share one set of records and the
+// two Adagrad launches one state, which only the timing reads.
+void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
+                const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
+  namespace k = xps::kern;
+  const auto kSr = k::Bf16Rounding::kStochastic;
+  size_t nstate = k::SparseLazyAdamStateFloats(kRows, kRowLen, true);
+  float* records;
+  uint16_t* table16;
+  CHECK(hipMalloc(reinterpret_cast<void**>(&records), nstate * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&table16), kRows * kRowLen * 2));
+  hipLaunchKernelGGL(fresh_kernel, dim3(4096), dim3(256), 0, nullptr, records, nstate,
+                     nstate / kRows);
+  // the bf16 table starts as the fp32 table, rounded to nearest
+  std::vector<uint64_t> h(kRows);
+  for (size_t i = 0; i < kRows; ++i) h[i] = i;
+  uint64_t* all;
+  CHECK(hipMalloc(reinterpret_cast<void**>(&all), kRows * 8));
+  CHECK(hipMemcpy(all, h.data(), kRows * 8, hipMemcpyHostToDevice));
+  k::SparseScatterAssignBf16(table16, all, kRows, kRowLen, table, nullptr, 0, 0, kRows);
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipFree(all));
+  for (int rotating = 0; rotating < 2; ++rotating) {
+    std::vector<float> us[6];
+    for (int r = -20; r < rounds; ++r) {
+      size_t turn = static_cast<size_t>(r + 20);
+      const uint64_t* kf = keys + (rotating ? ((turn + kSets / 2) % kSets) * kHot : 0);
+      const uint64_t* kb = keys + (rotating ? (turn % kSets) * kHot : 0);
+      uint64_t seed = turn;
+      float t[6];
+      t[0] = TimeUs(e0, e1, [&] {
+        k::SparseAdagradF32(table, state, kf, kHot, kRowLen, grad, out, 0.01f, 1e-8f, true,
+                            nullptr, 0, 0, kRows);
+      });
+      t[1] = TimeUs(e0, e1, [&] {
+        k::SparseAdagradBf16(table16, state, kb, kHot, kRowLen, grad, out, 0.01f, 1e-8f, true, kSr,
+                             seed, nullptr, 0, 0, kRows);
+      });
+      t[2] = TimeUs(e0, e1, [&] {
+        k::SparseLazyAdamF32(table, records, kf, kHot, kRowLen, grad, out, 0.01f, 0.9f, 0.999f,
+                             1e-8f, true, nullptr, 0, 0, kRows);
+      });
+      t[3] = TimeUs(e0, e1, [&] {
+        k::SparseLazyAdamBf16(table16, records, kb, kHot, kRowLen, grad, out, 0.01f, 0.9f, 0.999f,
+                              1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
+      });
+      t[4] = TimeUs(e0, e1, [&] {
+        k::SparseGatherF32(table, kf, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+      });
+      t[5] = TimeUs(e0, e1, [&] {
+        k::SparseGatherBf16(table16, kb, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+      });
+      for (int i = 0; i < 6 && r >= 0; ++i) us[i].push_back(t[i]);
+    }
+    CHECK(hipGetLastError());
+    const char* names[6] = {"adagrad", "adagrad16", "adam", "adam16", "gather", "gather16"};
+    for (int i = 0; i < 6; ++i) Report(rotating ? "rotating" : "hot", names[i], &us[i]);
+  }
+  CHECK(hipFree(records));
+  CHECK(hipFree(table16));
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   int rounds = 500;
   const char* opt = nullptr;  // none: the default comparison
+  bool bf16 = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--rounds") && i + 1 < argc) {
       rounds = atoi(argv[++i]);
     } else if (!strcmp(argv[i], "--opt") && i + 1 < argc &&
                (!strcmp(argv[i + 1], "lazy_adam") || !strcmp(argv[i + 1], "rowwise_lazy_adam"))) {
       opt = argv[++i];
+    } else if (!strcmp(argv[i], "--bf16")) {
+      bf16 = true;
     } else {
-      fprintf(stderr, "usage: %s [--rounds N] [--opt lazy_adam|rowwise_lazy_adam]\n", argv[0]);
+      fprintf(stderr, "usage: %s [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16]\n",
+              argv[0]);
       return 2;
     }
   }
@@ -152,7 +226,11 @@ int main(int argc, char** argv) {
   CHECK(hipEventCreate(&e1));
   printf("# %zu x %zu table, %zu rows per step, %d rounds, microseconds\n", kRows, kRowLen, kHot,
          rounds);
-  printf("%-9s %-6s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
+  printf("%-9s %-9s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
+  if (bf16) {
+    Bf16Rounds(rounds, table, state, grad, out, keys, e0, e1);
+    return 0;
+  }
   if (opt) {
     AdamRounds(!strcmp(opt, "rowwise_lazy_adam"), rounds, table, state, grad, out, keys, e0, e1);
     return 0;

@@ -17,6 +17,9 @@ per-occurrence rows.
 
 Needs one MI355X.  Run:  python examples/python/train_embedding.py
                         [--optimizer rowwise_adagrad|adagrad|lazy_adam|rowwise_lazy_adam]
+                        [--table-dtype f32|bf16]
+--table-dtype bf16 keeps the table in bf16 (half the bytes per row) with
+stochastic rounding on every store; the messages stay fp32.
 """
 import argparse
 import sys
@@ -39,14 +42,17 @@ def main():
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--optimizer", default="rowwise_adagrad", choices=sorted(LR))
-    optimizer = ap.parse_args().optimizer
+    ap.add_argument("--table-dtype", default="f32", choices=["f32", "bf16"])
+    args = ap.parse_args()
+    optimizer = args.optimizer
     ps.setup_env(1, 1, root_port=9310, XPS_DEV_ID=0, XPS_POOL_GB=1)
     roles = (("scheduler", -1), ("joint", 0))
     ths = [threading.Thread(target=ps.start, kwargs=dict(role=r, device=d)) for r, d in roles]
     [t.start() for t in ths]
     [t.join() for t in ths]
     server = ps.KVServer(0)
-    server.set_gpu_sparse_handle(ROWS, DIM, optimizer=optimizer, lr=LR[optimizer], eps=1e-8)
+    server.set_gpu_sparse_handle(ROWS, DIM, optimizer=optimizer, lr=LR[optimizer], eps=1e-8,
+                                 table_dtype=args.table_dtype)
     worker = ps.KVWorker(0, 0)
 
     gen = torch.Generator().manual_seed(3)
@@ -94,7 +100,8 @@ def main():
     [t.start() for t in ths]
     [t.join() for t in ths]
     assert losses[-1] < 0.5 * losses[0], "the loss did not fall"
-    print("loss %.4f -> %.4f with %s on the server" % (losses[0], losses[-1], optimizer))
+    print("loss %.4f -> %.4f with %s on the server, %s table"
+          % (losses[0], losses[-1], optimizer, args.table_dtype))
 
 
 if __name__ == "__main__":

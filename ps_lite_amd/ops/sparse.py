@@ -65,14 +65,26 @@ def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, w
     return out_keys[:m], (None if grad is None else out_sums[:m]), inverse
 
 
-def sparse_adagrad(table, state, rows, grad, lr, eps=1e-8, out=None):
+def _is_bf16(table):
+    import torch
+
+    return table.dtype == torch.bfloat16
+
+
+def sparse_adagrad(table, state, rows, grad, lr, eps=1e-8, out=None, rounding="stochastic",
+                   seed=0):
     """One Adagrad step on table[rows[i]] with gradient grad[i], in one launch.
 
     Row-wise when state.dim() == 1 (state[row] += mean(g * g)), element-wise
     when state has the table's shape (state[row] += g * g); then
     table[row] -= lr * g / (sqrt(state) + eps). Rows must be unique; a row
     outside the table is skipped. With `out` the new rows are also written
-    to out[i] (zeros for a skipped row). Returns out, or table without one."""
+    to out[i] (zeros for a skipped row). Returns out, or table without one.
+
+    A torch.bfloat16 table (state, grad and out stay fp32) runs the same fp32
+    arithmetic and rounds once on the store: rounding="stochastic" (seeded by
+    `seed`; pass a new one every step) or "nearest"; out then holds the stored
+    values widened to fp32."""
     assert table.is_cuda and table.dim() == 2 and table.is_contiguous()
     assert state.is_cuda and state.is_contiguous()
     rowwise = state.dim() == 1
@@ -80,15 +92,18 @@ def sparse_adagrad(table, state, rows, grad, lr, eps=1e-8, out=None):
     assert rows.is_cuda and rows.dim() == 1
     assert grad.is_contiguous() and grad.shape == (rows.numel(), table.shape[1])
     assert out is None or (out.is_contiguous() and out.shape == grad.shape)
-    _core.k_sparse_adagrad_f32(table.data_ptr(), state.data_ptr(), rows.data_ptr(),
-                               rows.numel(), table.shape[1], grad.data_ptr(),
-                               0 if out is None else out.data_ptr(), lr, eps, rowwise,
-                               table_rows=table.shape[0])
+    args = (table.data_ptr(), state.data_ptr(), rows.data_ptr(), rows.numel(), table.shape[1],
+            grad.data_ptr(), 0 if out is None else out.data_ptr(), lr, eps, rowwise)
+    if _is_bf16(table):
+        _core.k_sparse_adagrad_bf16(*args, rounding=rounding, seed=seed,
+                                    table_rows=table.shape[0])
+    else:
+        _core.k_sparse_adagrad_f32(*args, table_rows=table.shape[0])
     return table if out is None else out
 
 
 def sparse_lazy_adam_state(table, rowwise=False):
-    """A fresh lazy-Adam state for `table`: a flat fp32 tensor of one record
+    """A fresh lazy-Adam state for `table` (fp32 or bf16): a flat fp32 tensor of one record
     per row, {p1, p2, v_row, 0} m[row_len] and, element-wise only, v[row_len],
     with p1 = p2 = 1 and zeros everywhere else."""
     import torch
@@ -101,7 +116,7 @@ def sparse_lazy_adam_state(table, rowwise=False):
 
 
 def sparse_lazy_adam(table, state, rows, grad, lr, beta1=0.9, beta2=0.999, eps=1e-8,
-                     rowwise=False, out=None):
+                     rowwise=False, out=None, rounding="stochastic", seed=0):
     """One sparse Adam step on table[rows[i]] with gradient grad[i], in one launch.
 
     The bias correction is each row's own: its record in `state`
@@ -111,15 +126,19 @@ def sparse_lazy_adam(table, state, rows, grad, lr, beta1=0.9, beta2=0.999, eps=1
     mean(g * g); then table[row] -= lr / (1 - p1) * m / (sqrt(v / (1 - p2)) +
     eps). Rows must be unique; a row outside the table is skipped. With `out`
     the new rows are also written to out[i] (zeros for a skipped row).
-    Returns out, or table without one."""
+    Returns out, or table without one. A torch.bfloat16 table takes `rounding`
+    and `seed` as sparse_adagrad does."""
     assert table.is_cuda and table.dim() == 2 and table.is_contiguous()
     assert state.is_cuda and state.dim() == 1 and state.is_contiguous()
     assert state.numel() == _core.sparse_lazy_adam_state_floats(*table.shape, rowwise)
     assert rows.is_cuda and rows.dim() == 1
     assert grad.is_contiguous() and grad.shape == (rows.numel(), table.shape[1])
     assert out is None or (out.is_contiguous() and out.shape == grad.shape)
-    _core.k_sparse_lazy_adam_f32(table.data_ptr(), state.data_ptr(), rows.data_ptr(),
-                                 rows.numel(), table.shape[1], grad.data_ptr(),
-                                 0 if out is None else out.data_ptr(), lr, beta1, beta2, eps,
-                                 rowwise, table_rows=table.shape[0])
+    args = (table.data_ptr(), state.data_ptr(), rows.data_ptr(), rows.numel(), table.shape[1],
+            grad.data_ptr(), 0 if out is None else out.data_ptr(), lr, beta1, beta2, eps, rowwise)
+    if _is_bf16(table):
+        _core.k_sparse_lazy_adam_bf16(*args, rounding=rounding, seed=seed,
+                                      table_rows=table.shape[0])
+    else:
+        _core.k_sparse_lazy_adam_f32(*args, table_rows=table.shape[0])
     return table if out is None else out
