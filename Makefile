@@ -96,7 +96,8 @@ mxfp8bench: build/csrc/kernels.hip.o build/csrc/mxfp8.hip.o build/bench_mxfp8.o
 # one-process timing of the fused Adagrad step against scatter-add + gather,
 # or with --opt of a lazy-Adam step against the Adagrad step (links
 # kernels.hip, sparse_opt.hip and sparse_bf16.hip only; --bf16 times the
-# bf16-table kernels beside their fp32 siblings): build/bench_sparse_adagrad
+# bf16-table kernels, fp32 and 16-bit wire, beside their fp32 siblings):
+# build/bench_sparse_adagrad
 build/bench_sparse_adagrad.o: examples/cpp/bench_sparse_adagrad.hip csrc/*.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_sparse_adagrad.hip -o build/bench_sparse_adagrad.o

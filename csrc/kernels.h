@@ -153,6 +153,41 @@ void SparseLazyAdamBf16(uint16_t* table, float* state, const uint64_t* rows_dev,
                         float beta1, float beta2, float eps, bool rowwise, Bf16Rounding rounding,
                         uint64_t seed, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
                         uint64_t table_rows = ~0ull, int grid_cap = 0);
+// The bf16-table ops with bf16 bits on the wire side too: gradients and
+// pushed values come as bf16 bits and are widened exactly, rows out are the
+// stored bits (0x0000 for a key outside the table). Fed bits b, a step or an
+// add leaves the table and state bits its sibling above leaves fed widen(b).
+// 8-element units (one 16 B access per array) need row_len % 8 == 0 and
+// table, grad/src and out (and an element-wise Adagrad state) 16 B-aligned;
+// else the whole call moves uint16_t against uint16_t. Everything else,
+// the std::invalid_argument cases included, is the sibling's.
+// out[r][:] = table[row(r)][:] as bits
+void SparseGatherBf16Wire(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                          size_t row_len, uint16_t* out, hipStream_t s, int key_shift = 0,
+                          uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
+// table[row(r)][:] = src[r][:] as bits: no rounding, the sender rounded
+void SparseScatterAssignBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                                 size_t row_len, const uint16_t* src, hipStream_t s,
+                                 int key_shift = 0, uint64_t row_base = 0,
+                                 uint64_t table_rows = ~0ull, int grid_cap = 0);
+// table[row(r)][c] = R(float(table[row(r)][c]) + float(src[r][c])), one fp32 add
+void SparseScatterAddBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                              size_t row_len, const uint16_t* src, Bf16Rounding rounding,
+                              uint64_t seed, hipStream_t s, int key_shift = 0,
+                              uint64_t row_base = 0, uint64_t table_rows = ~0ull,
+                              int grid_cap = 0);
+// SparseAdagradBf16 with g = float(grad bits); out[r][c] = the stored bits
+void SparseAdagradBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                           size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
+                           float eps, bool rowwise, Bf16Rounding rounding, uint64_t seed,
+                           hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
+                           uint64_t table_rows = ~0ull, int grid_cap = 0);
+// SparseLazyAdamBf16 with g = float(grad bits); out[r][c] = the stored bits
+void SparseLazyAdamBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                            size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
+                            float beta1, float beta2, float eps, bool rowwise,
+                            Bf16Rounding rounding, uint64_t seed, hipStream_t s, int key_shift = 0,
+                            uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
 // Worker side of the sparse ops (sparse_coalesce.hip): a batch's ids, in any
 // order and with any repetition, become the sorted unique keys the ops above
 // and the handlers want. ids compare as unsigned 64-bit values.
@@ -178,6 +213,14 @@ size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const fl
                       size_t grad_rows, size_t row_len, uint64_t* uniq_keys, float* sums_or_null,
                       int64_t* inverse, void* workspace, size_t workspace_bytes, hipStream_t s,
                       int grid_cap = 0);
+// SparseCoalesce with the sums as bf16 bits, what a 16-bit wire pushes: each
+// fp32 sum as above, rounded once to nearest even on the store. 8 sums move
+// as one 16 B store when row_len % 8 == 0 and grad and sums are 16 B-aligned.
+size_t SparseCoalesceBf16(const uint64_t* ids_dev, size_t n, int key_shift,
+                          const float* grad_or_null, size_t grad_rows, size_t row_len,
+                          uint64_t* uniq_keys, uint16_t* sums_or_null, int64_t* inverse,
+                          void* workspace, size_t workspace_bytes, hipStream_t s,
+                          int grid_cap = 0);
 
 // Batched segmented copy/accumulate: one launch serving up to
 // kMaxBatch (dst, src, nbytes) segments — the device-side slicing/merge

@@ -340,17 +340,30 @@ class PyKVServer {
   // "rowwise_lazy_adam" (the sparse Adam with per-row bias correction; there
   // is no dense "adam"). table_dtype "f32" or "bf16"; a bf16 table needs an
   // optimizer and takes rounding ("stochastic" or "nearest") and seed, which
-  // an fp32 table refuses. Bad arguments raise ValueError before the handler
-  // (and with it the GPU) is touched.
+  // an fp32 table refuses. wire_dtype "f32" or "bf16": with "bf16" pushed
+  // values and pulled rows are bf16 bits, which needs a bf16 table and an
+  // even row_len. Bad arguments raise ValueError before the handler (and with
+  // it the GPU) is touched.
   void SetGpuSparseHandle(size_t rows, size_t row_len, bool accumulate, int key_shift,
                           py::object optimizer, float lr, float eps, float init_acc, float beta1,
                           float beta2, const std::string& table_dtype,
-                          const std::string& rounding, uint64_t seed) {
+                          const std::string& rounding, uint64_t seed,
+                          const std::string& wire_dtype) {
     SparseOptConfig opt;
     if (table_dtype == "bf16") {
       opt.table_dtype = SparseTableDtype::kBf16;
     } else if (table_dtype != "f32") {
       throw py::value_error("table_dtype must be \"f32\" or \"bf16\" (got \"" + table_dtype +
+                            "\")");
+    }
+    if (wire_dtype == "bf16") {
+      opt.wire_dtype = SparseTableDtype::kBf16;
+      if (opt.table_dtype != SparseTableDtype::kBf16) {
+        throw py::value_error("wire_dtype \"bf16\" needs table_dtype \"bf16\"");
+      }
+      if (row_len % 2) throw py::value_error("wire_dtype \"bf16\" needs an even row_len");
+    } else if (wire_dtype != "f32") {
+      throw py::value_error("wire_dtype must be \"f32\" or \"bf16\" (got \"" + wire_dtype +
                             "\")");
     }
     opt.rounding = ParseRounding(rounding);
@@ -636,7 +649,7 @@ PYBIND11_MODULE(_core, m) {
            py::arg("optimizer") = py::none(), py::arg("lr") = 0.01f, py::arg("eps") = 1e-8f,
            py::arg("init_acc") = 0.0f, py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f,
            py::arg("table_dtype") = "f32", py::arg("rounding") = "stochastic",
-           py::arg("seed") = 0)
+           py::arg("seed") = 0, py::arg("wire_dtype") = "f32")
       .def("register_entry", &PyKVServer::RegisterEntry, py::arg("key"), py::arg("ptr"),
            py::arg("nbytes"), py::arg("device") = 0)
       .def("sparse_table_ptr", &PyKVServer::SparseTablePtr)
@@ -1295,13 +1308,88 @@ PYBIND11_MODULE(_core, m) {
         py::arg("eps"), py::arg("rowwise"), py::arg("rounding") = "stochastic",
         py::arg("seed") = 0, py::arg("key_shift") = 0, py::arg("row_base") = 0,
         py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  // and with bf16 bits on the wire side too: out, src and grad hold bf16
+  // bits, the argument lists are the siblings'
+  auto u16 = [](uintptr_t p) { return reinterpret_cast<uint16_t*>(p); };
+  auto u64 = [](uintptr_t p) { return reinterpret_cast<uint64_t*>(p); };
+  m.def("k_sparse_gather_bf16_wire",
+        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
+            int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseGatherBf16Wire(u16(table), u64(rows), nrows, row_len, u16(out), nullptr,
+                                     key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
+  m.def("k_sparse_scatter_assign_bf16_wire",
+        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
+            int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseScatterAssignBf16Wire(u16(table), u64(rows), nrows, row_len, u16(src),
+                                            nullptr, key_shift, row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+        py::arg("grid_cap") = 0);
+  m.def("k_sparse_scatter_add_bf16_wire",
+        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
+            const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
+            uint64_t table_rows, int grid_cap) {
+          kern::SparseScatterAddBf16Wire(u16(table), u64(rows), nrows, row_len, u16(src),
+                                         ParseRounding(rounding), seed, nullptr, key_shift,
+                                         row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
+        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
+        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("k_sparse_adagrad_bf16_wire",
+        [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+            uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise,
+            const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
+            uint64_t table_rows, int grid_cap) {
+          kern::SparseAdagradBf16Wire(u16(table), reinterpret_cast<float*>(state), u64(rows),
+                                      nrows, row_len, u16(grad), u16(out), lr, eps, rowwise,
+                                      ParseRounding(rounding), seed, nullptr, key_shift, row_base,
+                                      table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
+        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
+        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  m.def("k_sparse_lazy_adam_bf16_wire",
+        [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+            uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
+            bool rowwise, const std::string& rounding, uint64_t seed, int key_shift,
+            uint64_t row_base, uint64_t table_rows, int grid_cap) {
+          kern::SparseLazyAdamBf16Wire(u16(table), reinterpret_cast<float*>(state), u64(rows),
+                                       nrows, row_len, u16(grad), u16(out), lr, beta1, beta2, eps,
+                                       rowwise, ParseRounding(rounding), seed, nullptr, key_shift,
+                                       row_base, table_rows, grid_cap);
+          gpu::DeviceSync(-1);
+        },
+        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("rowwise"), py::arg("rounding") = "stochastic",
+        py::arg("seed") = 0, py::arg("key_shift") = 0, py::arg("row_base") = 0,
+        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
   // ids -> sorted unique keys, summed rows, slot per occurrence (kernels.h);
   // returns the number of unique keys. grad = 0: no gradients, sums = 0: no
-  // sums. A bad argument raises ValueError before any GPU call.
+  // sums; sums_bf16: sums holds bf16 bits, each fp32 sum rounded to nearest
+  // even. A bad argument raises ValueError before any GPU call.
   m.def("k_sparse_coalesce",
         [](uintptr_t ids, size_t n, int key_shift, uintptr_t grad, size_t grad_rows,
            size_t row_len, uintptr_t uniq_keys, uintptr_t sums, uintptr_t inverse,
-           uintptr_t workspace, size_t workspace_bytes, int grid_cap) {
+           uintptr_t workspace, size_t workspace_bytes, int grid_cap, bool sums_bf16) {
+          if (sums_bf16) {
+            return kern::SparseCoalesceBf16(
+                reinterpret_cast<uint64_t*>(ids), n, key_shift, reinterpret_cast<float*>(grad),
+                grad_rows, row_len, reinterpret_cast<uint64_t*>(uniq_keys),
+                reinterpret_cast<uint16_t*>(sums), reinterpret_cast<int64_t*>(inverse),
+                reinterpret_cast<void*>(workspace), workspace_bytes, nullptr, grid_cap);
+          }
           return kern::SparseCoalesce(
               reinterpret_cast<uint64_t*>(ids), n, key_shift, reinterpret_cast<float*>(grad),
               grad_rows, row_len, reinterpret_cast<uint64_t*>(uniq_keys),
@@ -1311,7 +1399,7 @@ PYBIND11_MODULE(_core, m) {
         py::arg("ids"), py::arg("n"), py::arg("key_shift"), py::arg("grad"),
         py::arg("grad_rows"), py::arg("row_len"), py::arg("uniq_keys"), py::arg("sums"),
         py::arg("inverse"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("grid_cap") = 0);
+        py::arg("grid_cap") = 0, py::arg("sums_bf16") = false);
   m.def("sparse_coalesce_workspace_bytes", &kern::SparseCoalesceWorkspaceBytes, py::arg("n"));
   m.attr("coalesce_tile") = kern::SparseCoalesceTile();
 

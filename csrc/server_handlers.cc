@@ -750,6 +750,8 @@ GpuSparseHandler::GpuSparseHandler(Postoffice* po, size_t rows, size_t row_len, 
     row_base_ = (begin >> key_shift_) + ((begin & low) ? 1 : 0);
   }
   XPS_CHECK(!bf16() || has_opt) << "a bf16 sparse table needs an optimizer";
+  XPS_CHECK(!wire16() || (bf16() && row_len % 2 == 0))
+      << "a bf16 wire needs a bf16 sparse table and an even row_len";
   XPS_HIP_CHECK(hipSetDevice(pool->device()));
   table_ = pool->AllocArray(rows * row_len * (bf16() ? sizeof(uint16_t) : sizeof(float)));
   XPS_HIP_CHECK(hipMemset(table_.data(), 0, table_.size()));
@@ -806,7 +808,7 @@ void GpuSparseHandler::RespondRows(const KVMeta& req, const SArray<char>& out, s
   // keys stay meta-only: device keys must not be dereferenced host-side
   res.vals = SArray<float>::View(out);
   SArray<int> lens(1);
-  lens[0] = static_cast<int>(n * row_len_);
+  lens[0] = static_cast<int>(wire_bytes(n) / sizeof(float));
   res.lens = lens;
   // drained whenever no destination was advertised; the dense handlers'
   // HbmDest also drains for a host-pool destination
@@ -817,9 +819,13 @@ void GpuSparseHandler::RespondRows(const KVMeta& req, const SArray<char>& out, s
 // gather the n rows on `stream` and answer the pull with them
 void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, size_t n,
                                      hipStream_t stream, KVServer<float>* server) {
-  SArray<char> out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
+  SArray<char> out = HbmPool::Get()->AllocArray(wire_bytes(n));
   OrderAfter(stream);
-  if (bf16()) {
+  if (wire16()) {
+    kern::SparseGatherBf16Wire(reinterpret_cast<const uint16_t*>(table_.data()), rows, n, row_len_,
+                               reinterpret_cast<uint16_t*>(out.data()), stream, key_shift_,
+                               row_base_, rows_);
+  } else if (bf16()) {
     kern::SparseGatherBf16(reinterpret_cast<const uint16_t*>(table_.data()), rows, n, row_len_,
                            reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_,
                            rows_);
@@ -838,18 +844,29 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
   size_t n = kvs.keys.size();
   float* table = reinterpret_cast<float*>(table_.data());
   uint16_t* table16 = reinterpret_cast<uint16_t*>(table_.data());
+  // a bf16 wire: the pushed floats are pairs of bf16 bits
+  const uint16_t* vals16 = reinterpret_cast<const uint16_t*>(kvs.vals.data());
   XPS_CHECK(req.cmd == kCmdDefault || req.cmd == kCmdAssign || req.cmd == kCmdSum)
       << "optimizer sparse handler: cmd " << req.cmd << " names no operation";
   if (req.cmd == kCmdDefault) {
     // the gradient step; a fused round takes its response rows from the
     // same launch
     SArray<char> out;
-    if (req.pull) out = HbmPool::Get()->AllocArray(n * row_len_ * sizeof(float));
+    if (req.pull) out = HbmPool::Get()->AllocArray(wire_bytes(n));
     OrderAfter(stream);
     float* out_rows = req.pull ? reinterpret_cast<float*>(out.data()) : nullptr;
+    uint16_t* out16 = reinterpret_cast<uint16_t*>(out_rows);
     float* state = reinterpret_cast<float*>(state_.data());
     float lr = lr_.load(std::memory_order_relaxed);
-    if (bf16() && lazy_adam()) {
+    if (wire16() && lazy_adam()) {
+      kern::SparseLazyAdamBf16Wire(table16, state, rows, n, row_len_, vals16, out16, lr, opt_.beta1,
+                                   opt_.beta2, opt_.eps, rowwise(), opt_.rounding, NextSeed(),
+                                   stream, key_shift_, row_base_, rows_);
+    } else if (wire16()) {
+      kern::SparseAdagradBf16Wire(table16, state, rows, n, row_len_, vals16, out16, lr, opt_.eps,
+                                  rowwise(), opt_.rounding, NextSeed(), stream, key_shift_,
+                                  row_base_, rows_);
+    } else if (bf16() && lazy_adam()) {
       kern::SparseLazyAdamBf16(table16, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
                                opt_.beta1, opt_.beta2, opt_.eps, rowwise(), opt_.rounding,
                                NextSeed(), stream, key_shift_, row_base_, rows_);
@@ -872,7 +889,13 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     }
   } else {
     OrderAfter(stream);
-    if (bf16() && req.cmd == kCmdSum) {
+    if (wire16() && req.cmd == kCmdSum) {
+      kern::SparseScatterAddBf16Wire(table16, rows, n, row_len_, vals16, opt_.rounding, NextSeed(),
+                                     stream, key_shift_, row_base_, rows_);
+    } else if (wire16()) {
+      kern::SparseScatterAssignBf16Wire(table16, rows, n, row_len_, vals16, stream, key_shift_,
+                                        row_base_, rows_);
+    } else if (bf16() && req.cmd == kCmdSum) {
       kern::SparseScatterAddBf16(table16, rows, n, row_len_, kvs.vals.data(), opt_.rounding,
                                  NextSeed(), stream, key_shift_, row_base_, rows_);
     } else if (bf16()) {
@@ -904,7 +927,7 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
   float* table = reinterpret_cast<float*>(table_.data());
   if (req.push) {
     XPS_CHECK(kvs.vals.on_device()) << "sparse push needs device vals (pool buffers)";
-    XPS_CHECK_EQ(kvs.vals.size(), n * row_len_);
+    XPS_CHECK_EQ(kvs.vals.size(), wire_bytes(n) / sizeof(float));
     const uint64_t* rows = DeviceKeys(kvs.keys, req.sender, stream);
     if (opt_.kind != SparseOpt::kNone) {
       OptimizerPush(req, kvs, rows, stream, server);

@@ -175,8 +175,13 @@ class GpuDenseHandler {
 // kCmdSum = add (state untouched). `accumulate` plays no part then.
 //
 // A bf16 table (SparseTableDtype::kBf16; needs an optimizer) holds
-// rows * row_len * 2 bytes and goes through kern::Sparse*Bf16. The wire does
-// not change: pushes and pull responses stay fp32, lens count floats. The
+// rows * row_len * 2 bytes and goes through kern::Sparse*Bf16. By default
+// the wire does not change: pushes and pull responses stay fp32. With
+// wire_dtype kBf16 (needs a bf16 table and an even row_len) every pushed
+// value and every pulled row is bf16 bits, through kern::Sparse*Bf16Wire:
+// a row is row_len / 2 of the floats that lens and vals.size() count, a pull
+// is exact, and a step leaves the bits the fp32 wire leaves for the same
+// gradient values. Nothing of it is checkpointed. The
 // n-th launch that rounds (a step or an add; n counts from 0 and is
 // checkpointed) gets kern::SparseBf16LaunchSeed(seed, n), so a replayed
 // message sequence reproduces the table bit for bit. Without an optimizer
@@ -195,6 +200,7 @@ struct SparseOptConfig {
   SparseTableDtype table_dtype = SparseTableDtype::kF32;
   kern::Bf16Rounding rounding = kern::Bf16Rounding::kStochastic;  // bf16 table: the store rule
   uint64_t seed = 0;                                              // bf16 table, stochastic
+  SparseTableDtype wire_dtype = SparseTableDtype::kF32;  // what pushes and pulls carry
 };
 
 class GpuSparseHandler {
@@ -253,6 +259,11 @@ class GpuSparseHandler {
   void OrderAfter(hipStream_t s);
   void Publish(hipStream_t s);
   bool bf16() const { return opt_.table_dtype == SparseTableDtype::kBf16; }
+  bool wire16() const { return opt_.wire_dtype == SparseTableDtype::kBf16; }
+  // a message's n rows on the wire, in bytes
+  size_t wire_bytes(size_t n) const {
+    return n * row_len_ * (wire16() ? sizeof(uint16_t) : sizeof(float));
+  }
   // the seed of the next launch that rounds; counts it
   uint64_t NextSeed() { return kern::SparseBf16LaunchSeed(opt_.seed, launches_.fetch_add(1)); }
 

@@ -1,9 +1,12 @@
 // The sparse handler's kernels over a bf16 embedding table for CDNA4
 // (gfx950): gather, assign, add, and the Adagrad and lazy-Adam steps of
-// sparse_opt.hip with the weights stored as bf16 bits. Gradients, optimizer
-// state, the returned rows and the pushed values stay fp32; a step widens
-// the weight exactly, runs sparse_elem.h's fp32 arithmetic unchanged, and
-// rounds once on the store.
+// sparse_opt.hip with the weights stored as bf16 bits. The optimizer state
+// stays fp32; a step widens the weight exactly, runs sparse_elem.h's fp32
+// arithmetic unchanged, and rounds once on the store. The wire side (the
+// gradients and pushed values, the returned rows) is fp32 (Sparse*Bf16) or
+// bf16 bits (Sparse*Bf16Wire): a 16-bit gradient is widened exactly and a
+// 16-bit row out is the stored bits, so the two wires leave the same table
+// and state bits for the same values.
 //
 // The store rule R(x), u the bits of x: nearest is round-to-nearest-even;
 // stochastic stores (u + r) >> 16 with r uniform in [0, 2^16), so the
@@ -32,12 +35,17 @@
 // time. The scalar path (row_len % 8 != 0 or a pointer off its 16 B
 // boundary) is the same body with a unit of one element, uint16_t against
 // float, for the whole call.
+// With a 16-bit wire every row array of a unit is one 16 B access, and a
+// resident gradient unit stays packed, 4 registers, until its row's scalars
+// are known; the scalar path moves uint16_t against uint16_t.
 // Traffic per row of L elements, by construction: row-wise Adagrad with out
-// 12 L bytes (fp32: 16 L), row-wise lazy Adam 20 L + 32 (24 L + 32), gather
-// 6 L (8 L).
+// 12 L bytes (fp32 table: 16 L; 16-bit wire: 8 L), row-wise lazy Adam
+// 20 L + 32 (24 L + 32; 16 L + 32), gather 6 L (8 L; 4 L).
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
+#include <string>
+#include <type_traits>
 
 #include "kernels.h"
 #include "sparse_elem.h"
@@ -47,7 +55,10 @@ namespace kern {
 
 namespace {
 
-constexpr int kKeep = 2;  // resident units of a lane: 16 elements of each array
+// resident units of a lane: 16 elements of each array. 4 was measured for the
+// 16-bit wire's smaller gradient unit (profiles/sparse_bf16_wire.md): faster
+// at row length 2048, slower at 64 on both wires, so it stays 2.
+constexpr int kKeep = 2;
 constexpr uint64_t kPhi = 0x9E3779B97F4A7C15ull;
 
 __host__ __device__ inline uint64_t Mix64(uint64_t z) {
@@ -122,6 +133,42 @@ struct Unit<1> {
   static __device__ inline void StoreF(float* p, const float (&x)[1]) { *p = x[0]; }
 };
 
+// The wire side of a unit: the gradient or pushed values in, the rows out.
+// Held is what a lane keeps of a unit it has loaded, Open its fp32 values;
+// Store writes a unit of rows out, given both its values x and their bits.
+template <int kN>
+struct F32Wire {
+  using T = float;
+  struct Held {
+    float x[kN];
+  };
+  static __device__ inline Held Load(const float* p) {
+    Held h;
+    Unit<kN>::LoadF(p, h.x);
+    return h;
+  }
+  static __device__ inline void Open(const Held& h, float (&x)[kN]) {
+#pragma unroll
+    for (int j = 0; j < kN; ++j) x[j] = h.x[j];
+  }
+  static __device__ inline void Store(float* p, const float (&x)[kN], typename Unit<kN>::Packed) {
+    Unit<kN>::StoreF(p, x);
+  }
+};
+template <int kN>
+struct Bf16Wire {
+  using T = uint16_t;
+  using Held = typename Unit<kN>::Packed;
+  static __device__ inline Held Load(const uint16_t* p) { return Unit<kN>::LoadW(p); }
+  static __device__ inline void Open(Held h, float (&x)[kN]) { Unit<kN>::Unpack(h, x); }
+  static __device__ inline void Store(uint16_t* p, const float (&)[kN], Held bits) {
+    Unit<kN>::StoreW(p, bits);
+  }
+};
+// the two wires by the type of their arrays
+template <class T, int kN>
+using WireOf = std::conditional_t<std::is_same<T, float>::value, F32Wire<kN>, Bf16Wire<kN>>;
+
 // R over unit c of a row: the packed bits to store, x left as those bits
 // widened (what a later gather returns)
 template <int kN>
@@ -159,12 +206,15 @@ struct MoveArgs {
   Rounding rd;
 };
 
-// one unit of one message row per lane and step, grid-stride; f is the fp32
-// side: out (gather), src (assign, add)
-template <int kN, Move kOp>
+// one unit of one message row per lane and step, grid-stride; f is the wire
+// side: out (gather), src (assign, add). A 16-bit gather and assign move
+// bits: the worker rounded what it assigns.
+template <int kN, Move kOp, class T>
 __global__ void __launch_bounds__(kBlock)
-    sparse_move_bf16_kernel(uint16_t* __restrict__ table, float* __restrict__ f, MoveArgs a) {
+    sparse_move_bf16_kernel(uint16_t* __restrict__ table, T* __restrict__ f, MoveArgs a) {
   using U = Unit<kN>;
+  using W = WireOf<T, kN>;
+  using Packed = typename U::Packed;
   const size_t total = a.nrows * a.nv;
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < total;
@@ -176,17 +226,23 @@ __global__ void __launch_bounds__(kBlock)
     if (!ok) {
       if (kOp == Move::kGather) {
         Zero(x);
-        U::StoreF(f + i * kN, x);
+        W::Store(f + i * kN, x, Packed{});
       }
       continue;
     }
     uint16_t* tp = table + (row * a.nv + c) * kN;
     if (kOp == Move::kGather) {
-      U::Unpack(U::LoadW(tp), x);
-      U::StoreF(f + i * kN, x);
+      const Packed p = U::LoadW(tp);
+      U::Unpack(p, x);
+      W::Store(f + i * kN, x, p);
       continue;
     }
-    U::LoadF(f + i * kN, x);
+    const typename W::Held h = W::Load(f + i * kN);
+    if constexpr (kOp == Move::kAssign && std::is_same<T, uint16_t>::value) {
+      U::StoreW(tp, h);
+      continue;
+    }
+    W::Open(h, x);
     if (kOp == Move::kAdd) {
       float w[kN];
       U::Unpack(U::LoadW(tp), w);
@@ -198,19 +254,18 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <Move kOp>
-void LaunchMove(uint16_t* table, float* f, size_t row_len, MoveArgs a, int grid_cap,
-                hipStream_t s) {
+template <Move kOp, class T>
+void LaunchMove(uint16_t* table, T* f, size_t row_len, MoveArgs a, int grid_cap, hipStream_t s) {
   if (a.nrows == 0 || row_len == 0) return;
   const bool vec = row_len % 8 == 0 && Aligned16(table) && Aligned16(f);
   a.nv = vec ? row_len / 8 : row_len;
   int grid = GridFor(a.nrows * a.nv, 16384, grid_cap);
   if (vec) {
-    hipLaunchKernelGGL((sparse_move_bf16_kernel<8, kOp>), dim3(grid), dim3(kBlock), 0, s, table, f,
-                       a);
+    hipLaunchKernelGGL((sparse_move_bf16_kernel<8, kOp, T>), dim3(grid), dim3(kBlock), 0, s, table,
+                       f, a);
   } else {
-    hipLaunchKernelGGL((sparse_move_bf16_kernel<1, kOp>), dim3(grid), dim3(kBlock), 0, s, table, f,
-                       a);
+    hipLaunchKernelGGL((sparse_move_bf16_kernel<1, kOp, T>), dim3(grid), dim3(kBlock), 0, s, table,
+                       f, a);
   }
 }
 
@@ -252,6 +307,12 @@ __device__ inline float SumSq(const float (&g)[kN]) {
   for (int j = 0; j < kN; ++j) ss += g[j] * g[j];
   return ss;
 }
+template <class W, int kN>
+__device__ inline float SumSqOf(const typename W::Held& h) {
+  float g[kN];
+  W::Open(h, g);
+  return SumSq(g);
+}
 
 // what a lane knows of its row in one pass of the wave's loop
 struct RowAt {
@@ -270,20 +331,21 @@ __device__ inline RowAt Locate(const StepArgs& a, size_t first, int lane) {
 }
 
 // the gather's defined output for a key outside the table
-template <int kN>
-__device__ inline void ZeroRow(float* out, size_t nv, int gl, int G) {
+template <class W, int kN>
+__device__ inline void ZeroRow(typename W::T* out, size_t nv, int gl, int G) {
   float z[kN];
   Zero(z);
-  for (size_t c = gl; c < nv; c += G) Unit<kN>::StoreF(out + c * kN, z);
+  for (size_t c = gl; c < nv; c += G) W::Store(out + c * kN, z, typename Unit<kN>::Packed{});
 }
 
-template <int kN, bool kRowwise>
+template <int kN, bool kRowwise, class T>
 __global__ void __launch_bounds__(kBlock)
     sparse_adagrad_bf16_kernel(uint16_t* __restrict__ table, float* __restrict__ state,
-                               const float* __restrict__ grad, float* __restrict__ out,
-                               StepArgs a) {
+                               const T* __restrict__ grad, T* __restrict__ out, StepArgs a) {
   using U = Unit<kN>;
+  using W = WireOf<T, kN>;
   using Packed = typename U::Packed;
+  using Held = typename W::Held;
   const int G = 1 << a.log2g;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);  // lane within the row's group
@@ -297,34 +359,30 @@ __global__ void __launch_bounds__(kBlock)
   // wave-uniform bounds: every lane of the wave reaches the shuffles
   for (size_t first = wave * rows_per_wave; first < a.nrows; first += nwaves * rows_per_wave) {
     const RowAt at = Locate(a, first, lane);
-    const float* gp = grad + (at.live ? at.r * len : 0);
+    const T* gp = grad + (at.live ? at.r * len : 0);
     uint16_t* tp = table + (at.ok ? at.row * len : 0);
     float* sp = kRowwise ? nullptr : state + (at.ok ? at.row * len : 0);
 
     // every resident unit of the row in one batch
-    float g[kKeep][kN], st[kRowwise ? 1 : kKeep][kN];
+    Held g[kKeep] = {};
+    float st[kRowwise ? 1 : kKeep][kN];
     Packed w[kKeep] = {};
     float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < kKeep; ++k) {
       const size_t c = gl + (static_cast<size_t>(k) << a.log2g);
-      Zero(g[k]);
       if (at.ok && c < nv) {
-        U::LoadF(gp + c * kN, g[k]);
+        g[k] = W::Load(gp + c * kN);
         w[k] = U::LoadW(tp + c * kN);
         if (!kRowwise) U::LoadF(sp + c * kN, st[kRowwise ? 0 : k]);
       }
-      if (kRowwise) ss += SumSq(g[k]);
+      if (kRowwise) ss += SumSqOf<W, kN>(g[k]);
     }
 
     float denom = 0.f;
     if (kRowwise) {
       if (at.ok) {
-        float gv[kN];
-        for (size_t c = resident + gl; c < nv; c += G) {
-          U::LoadF(gp + c * kN, gv);
-          ss += SumSq(gv);
-        }
+        for (size_t c = resident + gl; c < nv; c += G) ss += SumSqOf<W, kN>(W::Load(gp + c * kN));
       }
       for (int m = G >> 1; m > 0; m >>= 1) ss += __shfl_xor(ss, m);
       float s = 0.f;
@@ -337,14 +395,15 @@ __global__ void __launch_bounds__(kBlock)
     }
 
     if (!at.live) continue;  // past the shuffles: nothing below crosses lanes
-    float* op = out ? out + at.r * len : nullptr;
+    T* op = out ? out + at.r * len : nullptr;
     if (!at.ok) {
-      if (out) ZeroRow<kN>(op, nv, gl, G);
+      if (out) ZeroRow<W, kN>(op, nv, gl, G);
       continue;
     }
     const uint64_t row_key = a.rd.stochastic ? RowKey(a.rd, at.row) : 0;
-    auto apply = [&](size_t c, const float (&gv)[kN], Packed wv, float (&sv)[kN]) {
-      float x[kN];
+    auto apply = [&](size_t c, const Held& gh, Packed wv, float (&sv)[kN]) {
+      float x[kN], gv[kN];
+      W::Open(gh, gv);
       U::Unpack(wv, x);
 #pragma unroll
       for (int j = 0; j < kN; ++j) {
@@ -356,8 +415,9 @@ __global__ void __launch_bounds__(kBlock)
         }
       }
       if (!kRowwise) U::StoreF(sp + c * kN, sv);
-      U::StoreW(tp + c * kN, Round<kN>(x, c, row_key, a.rd.stochastic));
-      if (out) U::StoreF(op + c * kN, x);
+      const Packed bits = Round<kN>(x, c, row_key, a.rd.stochastic);
+      U::StoreW(tp + c * kN, bits);
+      if (out) W::Store(op + c * kN, x, bits);
     };
 #pragma unroll
     for (int k = 0; k < kKeep; ++k) {
@@ -365,23 +425,24 @@ __global__ void __launch_bounds__(kBlock)
       if (c < nv) apply(c, g[k], w[k], st[kRowwise ? 0 : k]);
     }
     for (size_t c = resident + gl; c < nv; c += G) {
-      float gv[kN], sv[kN];
-      U::LoadF(gp + c * kN, gv);
+      float sv[kN];
+      const Held gh = W::Load(gp + c * kN);
       if (!kRowwise) U::LoadF(sp + c * kN, sv);
-      apply(c, gv, U::LoadW(tp + c * kN), sv);
+      apply(c, gh, U::LoadW(tp + c * kN), sv);
     }
   }
 }
 
 // The operations and their order are sparse_opt.hip's lazy Adam; the record
 // layout is SparseLazyAdamF32's.
-template <int kN, bool kRowwise>
+template <int kN, bool kRowwise, class T>
 __global__ void __launch_bounds__(kBlock)
     sparse_lazy_adam_bf16_kernel(uint16_t* __restrict__ table, float* __restrict__ state,
-                                 const float* __restrict__ grad, float* __restrict__ out,
-                                 StepArgs a) {
+                                 const T* __restrict__ grad, T* __restrict__ out, StepArgs a) {
   using U = Unit<kN>;
+  using W = WireOf<T, kN>;
   using Packed = typename U::Packed;
+  using Held = typename W::Held;
   constexpr bool kVec = kN == 8;
   const int G = 1 << a.log2g;
   const int lane = threadIdx.x & 63;
@@ -397,7 +458,7 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t first = wave * rows_per_wave; first < a.nrows; first += nwaves * rows_per_wave) {
     const RowAt at = Locate(a, first, lane);
     const bool lead = at.ok && gl == 0;
-    const float* gp = grad + (at.live ? at.r * len : 0);
+    const T* gp = grad + (at.live ? at.r * len : 0);
     uint16_t* tp = table + (at.ok ? at.row * len : 0);
     float* rec = state + (at.ok ? at.row * a.rec : 0);
     float* mp = rec + 4;
@@ -406,28 +467,24 @@ __global__ void __launch_bounds__(kBlock)
     // the header first, then every resident unit of the row in one batch
     float4 h{1.f, 1.f, 0.f, 0.f};
     if (lead) h = LoadHeader<kVec>(rec);
-    float g[kKeep][kN], m[kKeep][kN], v[kRowwise ? 1 : kKeep][kN];
+    Held g[kKeep] = {};
+    float m[kKeep][kN], v[kRowwise ? 1 : kKeep][kN];
     Packed w[kKeep] = {};
     float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < kKeep; ++k) {
       const size_t c = gl + (static_cast<size_t>(k) << a.log2g);
-      Zero(g[k]);
       if (at.ok && c < nv) {
-        U::LoadF(gp + c * kN, g[k]);
+        g[k] = W::Load(gp + c * kN);
         w[k] = U::LoadW(tp + c * kN);
         U::LoadF(mp + c * kN, m[k]);
         if (!kRowwise) U::LoadF(vp + c * kN, v[kRowwise ? 0 : k]);
       }
-      if (kRowwise) ss += SumSq(g[k]);
+      if (kRowwise) ss += SumSqOf<W, kN>(g[k]);
     }
     if (kRowwise) {
       if (at.ok) {
-        float gv[kN];
-        for (size_t c = resident + gl; c < nv; c += G) {
-          U::LoadF(gp + c * kN, gv);
-          ss += SumSq(gv);
-        }
+        for (size_t c = resident + gl; c < nv; c += G) ss += SumSqOf<W, kN>(W::Load(gp + c * kN));
       }
       for (int x = G >> 1; x > 0; x >>= 1) ss += __shfl_xor(ss, x);
     }
@@ -449,15 +506,15 @@ __global__ void __launch_bounds__(kBlock)
     q = __shfl(q, lane - gl);
 
     if (!at.live) continue;  // past the shuffles: nothing below crosses lanes
-    float* op = out ? out + at.r * len : nullptr;
+    T* op = out ? out + at.r * len : nullptr;
     if (!at.ok) {
-      if (out) ZeroRow<kN>(op, nv, gl, G);
+      if (out) ZeroRow<W, kN>(op, nv, gl, G);
       continue;
     }
     const uint64_t row_key = a.rd.stochastic ? RowKey(a.rd, at.row) : 0;
-    auto apply = [&](size_t c, const float (&gv)[kN], Packed wv, float (&mv)[kN],
-                     float (&vv)[kN]) {
-      float x[kN];
+    auto apply = [&](size_t c, const Held& gh, Packed wv, float (&mv)[kN], float (&vv)[kN]) {
+      float x[kN], gv[kN];
+      W::Open(gh, gv);
       U::Unpack(wv, x);
 #pragma unroll
       for (int j = 0; j < kN; ++j) {
@@ -471,8 +528,9 @@ __global__ void __launch_bounds__(kBlock)
       }
       U::StoreF(mp + c * kN, mv);
       if (!kRowwise) U::StoreF(vp + c * kN, vv);
-      U::StoreW(tp + c * kN, Round<kN>(x, c, row_key, a.rd.stochastic));
-      if (out) U::StoreF(op + c * kN, x);
+      const Packed bits = Round<kN>(x, c, row_key, a.rd.stochastic);
+      U::StoreW(tp + c * kN, bits);
+      if (out) W::Store(op + c * kN, x, bits);
     };
 #pragma unroll
     for (int k = 0; k < kKeep; ++k) {
@@ -480,37 +538,37 @@ __global__ void __launch_bounds__(kBlock)
       if (c < nv) apply(c, g[k], w[k], m[k], v[kRowwise ? 0 : k]);
     }
     for (size_t c = resident + gl; c < nv; c += G) {
-      float gv[kN], mv[kN], vv[kN];
-      U::LoadF(gp + c * kN, gv);
+      float mv[kN], vv[kN];
+      const Held gh = W::Load(gp + c * kN);
       U::LoadF(mp + c * kN, mv);
       if (!kRowwise) U::LoadF(vp + c * kN, vv);
-      apply(c, gv, U::LoadW(tp + c * kN), mv, vv);
+      apply(c, gh, U::LoadW(tp + c * kN), mv, vv);
     }
   }
 }
 
 enum class Opt { kAdagrad, kLazyAdam };
 
-template <Opt kOpt, int kN, bool kRowwise>
-void LaunchStepAs(uint16_t* table, float* state, const float* grad, float* out, StepArgs a,
-                  int grid_cap, hipStream_t s) {
+template <Opt kOpt, int kN, bool kRowwise, class T>
+void LaunchStepAs(uint16_t* table, float* state, const T* grad, T* out, StepArgs a, int grid_cap,
+                  hipStream_t s) {
   while ((size_t{1} << a.log2g) < a.nv && a.log2g < 6) ++a.log2g;
   size_t rows_per_wave = 64 >> a.log2g;
   size_t waves = (a.nrows + rows_per_wave - 1) / rows_per_wave;
   // the sparse kernels' grid: enough blocks for the 8 XCDs, at most 16384
   int grid = GridFor(waves * 64, 16384, grid_cap);
   if (kOpt == Opt::kAdagrad) {
-    hipLaunchKernelGGL((sparse_adagrad_bf16_kernel<kN, kRowwise>), dim3(grid), dim3(kBlock), 0, s,
-                       table, state, grad, out, a);
-  } else {
-    hipLaunchKernelGGL((sparse_lazy_adam_bf16_kernel<kN, kRowwise>), dim3(grid), dim3(kBlock), 0,
+    hipLaunchKernelGGL((sparse_adagrad_bf16_kernel<kN, kRowwise, T>), dim3(grid), dim3(kBlock), 0,
                        s, table, state, grad, out, a);
+  } else {
+    hipLaunchKernelGGL((sparse_lazy_adam_bf16_kernel<kN, kRowwise, T>), dim3(grid), dim3(kBlock),
+                       0, s, table, state, grad, out, a);
   }
 }
 
-template <Opt kOpt>
-void LaunchStep(uint16_t* table, float* state, const float* grad, float* out, size_t row_len,
-                bool vec, bool rowwise, StepArgs a, int grid_cap, hipStream_t s) {
+template <Opt kOpt, class T>
+void LaunchStep(uint16_t* table, float* state, const T* grad, T* out, size_t row_len, bool vec,
+                bool rowwise, StepArgs a, int grid_cap, hipStream_t s) {
   a.nv = vec ? row_len / 8 : row_len;
   if (vec && rowwise) {
     LaunchStepAs<kOpt, 8, true>(table, state, grad, out, a, grid_cap, s);
@@ -523,6 +581,101 @@ void LaunchStep(uint16_t* table, float* state, const float* grad, float* out, si
   }
 }
 
+// what the steps share of a call; T is the wire's element
+struct StepCall {
+  const char* name;
+  const uint64_t* rows;
+  size_t nrows, row_len;
+  bool rowwise;
+  Bf16Rounding rounding;
+  uint64_t seed;
+  hipStream_t s;
+  int key_shift;
+  uint64_t row_base, table_rows;
+  int grid_cap;
+};
+[[noreturn]] void Refuse(const StepCall& c, const char* what) {
+  throw std::invalid_argument(std::string(c.name) + ": " + what);
+}
+StepArgs MakeStep(const StepCall& c, float lr, float eps) {
+  StepArgs a{};
+  a.rows = c.rows;
+  a.nrows = c.nrows;
+  a.row_len = static_cast<float>(c.row_len);
+  a.lr = lr;
+  a.eps = eps;
+  a.shift = c.key_shift;
+  a.base = c.row_base;
+  a.tab_rows = c.table_rows;
+  a.rd = Rounding{c.seed, c.rounding == Bf16Rounding::kStochastic};
+  return a;
+}
+
+template <class T>
+void Adagrad(uint16_t* table, float* state, const T* grad, T* out_or_null, float lr, float eps,
+             const StepCall& c) {
+  if (!(lr > 0.f)) Refuse(c, "lr must be positive");
+  if (!(eps > 0.f)) Refuse(c, "eps must be positive");
+  if (c.nrows == 0 || c.row_len == 0) return;
+  // 8-element units need whole units and every array they move on a 16 B
+  // boundary (the row-wise state moves as single floats)
+  bool vec = c.row_len % 8 == 0 && Aligned16(table) && Aligned16(grad, out_or_null) &&
+             (c.rowwise || Aligned16(state));
+  LaunchStep<Opt::kAdagrad>(table, state, grad, out_or_null, c.row_len, vec, c.rowwise,
+                            MakeStep(c, lr, eps), c.grid_cap, c.s);
+}
+
+template <class T>
+void LazyAdam(uint16_t* table, float* state, const T* grad, T* out_or_null, float lr, float beta1,
+              float beta2, float eps, const StepCall& c) {
+  if (!(lr > 0.f)) Refuse(c, "lr must be positive");
+  if (!(eps > 0.f)) Refuse(c, "eps must be positive");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) {
+    Refuse(c, "beta1 and beta2 must lie in [0, 1)");
+  }
+  // every record's header is one 16 B access on the vector path
+  if (!Aligned16(state)) Refuse(c, "state must be 16 B-aligned");
+  if (c.nrows == 0 || c.row_len == 0) return;
+  StepArgs a = MakeStep(c, lr, eps);
+  a.rec = SparseLazyAdamStateFloats(1, c.row_len, c.rowwise);
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.omb1 = 1.f - beta1;
+  a.omb2 = 1.f - beta2;
+  // 8-element units need whole units and table, grad and out on a 16 B
+  // boundary; the records' moments then are, their length being a multiple
+  // of four floats
+  bool vec = c.row_len % 8 == 0 && Aligned16(table) && Aligned16(grad, out_or_null);
+  LaunchStep<Opt::kLazyAdam>(table, state, grad, out_or_null, c.row_len, vec, c.rowwise, a,
+                             c.grid_cap, c.s);
+}
+
+template <class T>
+void Gather(const uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len, T* out,
+            hipStream_t s, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  MoveArgs a =
+      MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, Bf16Rounding::kNearest, 0);
+  // the gather only reads the table
+  LaunchMove<Move::kGather>(const_cast<uint16_t*>(table), out, row_len, a, grid_cap, s);
+}
+
+template <class T>
+void Assign(uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len, const T* src,
+            hipStream_t s, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  MoveArgs a =
+      MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, Bf16Rounding::kNearest, 0);
+  // assign and add only read src
+  LaunchMove<Move::kAssign>(table, const_cast<T*>(src), row_len, a, grid_cap, s);
+}
+
+template <class T>
+void Add(uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len, const T* src,
+         Bf16Rounding rounding, uint64_t seed, hipStream_t s, int key_shift, uint64_t row_base,
+         uint64_t table_rows, int grid_cap) {
+  MoveArgs a = MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, rounding, seed);
+  LaunchMove<Move::kAdd>(table, const_cast<T*>(src), row_len, a, grid_cap, s);
+}
+
 }  // namespace
 
 uint64_t SparseBf16LaunchSeed(uint64_t seed, uint64_t n) { return Mix64(seed + (n + 1) * kPhi); }
@@ -530,50 +683,55 @@ uint64_t SparseBf16LaunchSeed(uint64_t seed, uint64_t n) { return Mix64(seed + (
 void SparseGatherBf16(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
                       size_t row_len, float* out, hipStream_t s, int key_shift, uint64_t row_base,
                       uint64_t table_rows, int grid_cap) {
-  MoveArgs a =
-      MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, Bf16Rounding::kNearest, 0);
-  // the gather only reads the table
-  LaunchMove<Move::kGather>(const_cast<uint16_t*>(table), out, row_len, a, grid_cap, s);
+  Gather(table, rows_dev, nrows, row_len, out, s, key_shift, row_base, table_rows, grid_cap);
+}
+void SparseGatherBf16Wire(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                          size_t row_len, uint16_t* out, hipStream_t s, int key_shift,
+                          uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  Gather(table, rows_dev, nrows, row_len, out, s, key_shift, row_base, table_rows, grid_cap);
 }
 
 void SparseScatterAssignBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
                              size_t row_len, const float* src, hipStream_t s, int key_shift,
                              uint64_t row_base, uint64_t table_rows, int grid_cap) {
-  MoveArgs a =
-      MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, Bf16Rounding::kNearest, 0);
-  // assign and add only read src
-  LaunchMove<Move::kAssign>(table, const_cast<float*>(src), row_len, a, grid_cap, s);
+  Assign(table, rows_dev, nrows, row_len, src, s, key_shift, row_base, table_rows, grid_cap);
+}
+void SparseScatterAssignBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                                 size_t row_len, const uint16_t* src, hipStream_t s, int key_shift,
+                                 uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  Assign(table, rows_dev, nrows, row_len, src, s, key_shift, row_base, table_rows, grid_cap);
 }
 
 void SparseScatterAddBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
                           const float* src, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
                           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-  MoveArgs a = MakeMove(rows_dev, nrows, key_shift, row_base, table_rows, rounding, seed);
-  LaunchMove<Move::kAdd>(table, const_cast<float*>(src), row_len, a, grid_cap, s);
+  Add(table, rows_dev, nrows, row_len, src, rounding, seed, s, key_shift, row_base, table_rows,
+      grid_cap);
+}
+void SparseScatterAddBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
+                              size_t row_len, const uint16_t* src, Bf16Rounding rounding,
+                              uint64_t seed, hipStream_t s, int key_shift, uint64_t row_base,
+                              uint64_t table_rows, int grid_cap) {
+  Add(table, rows_dev, nrows, row_len, src, rounding, seed, s, key_shift, row_base, table_rows,
+      grid_cap);
 }
 
 void SparseAdagradBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
                        size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
                        bool rowwise, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
                        int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-  if (!(lr > 0.f)) throw std::invalid_argument("SparseAdagradBf16: lr must be positive");
-  if (!(eps > 0.f)) throw std::invalid_argument("SparseAdagradBf16: eps must be positive");
-  if (nrows == 0 || row_len == 0) return;
-  StepArgs a{};
-  a.rows = rows_dev;
-  a.nrows = nrows;
-  a.row_len = static_cast<float>(row_len);
-  a.lr = lr;
-  a.eps = eps;
-  a.shift = key_shift;
-  a.base = row_base;
-  a.tab_rows = table_rows;
-  a.rd = Rounding{seed, rounding == Bf16Rounding::kStochastic};
-  // 8-element units need whole units and every array they move on a 16 B
-  // boundary (the row-wise state moves as single floats)
-  bool vec = row_len % 8 == 0 && Aligned16(table) && Aligned16(grad, out_or_null) &&
-             (rowwise || Aligned16(state));
-  LaunchStep<Opt::kAdagrad>(table, state, grad, out_or_null, row_len, vec, rowwise, a, grid_cap, s);
+  Adagrad(table, state, grad, out_or_null, lr, eps,
+          StepCall{"SparseAdagradBf16", rows_dev, nrows, row_len, rowwise, rounding, seed, s,
+                   key_shift, row_base, table_rows, grid_cap});
+}
+void SparseAdagradBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                           size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
+                           float eps, bool rowwise, Bf16Rounding rounding, uint64_t seed,
+                           hipStream_t s, int key_shift, uint64_t row_base, uint64_t table_rows,
+                           int grid_cap) {
+  Adagrad(table, state, grad, out_or_null, lr, eps,
+          StepCall{"SparseAdagradBf16Wire", rows_dev, nrows, row_len, rowwise, rounding, seed, s,
+                   key_shift, row_base, table_rows, grid_cap});
 }
 
 void SparseLazyAdamBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
@@ -581,37 +739,18 @@ void SparseLazyAdamBf16(uint16_t* table, float* state, const uint64_t* rows_dev,
                         float beta1, float beta2, float eps, bool rowwise, Bf16Rounding rounding,
                         uint64_t seed, hipStream_t s, int key_shift, uint64_t row_base,
                         uint64_t table_rows, int grid_cap) {
-  if (!(lr > 0.f)) throw std::invalid_argument("SparseLazyAdamBf16: lr must be positive");
-  if (!(eps > 0.f)) throw std::invalid_argument("SparseLazyAdamBf16: eps must be positive");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) {
-    throw std::invalid_argument("SparseLazyAdamBf16: beta1 and beta2 must lie in [0, 1)");
-  }
-  // every record's header is one 16 B access on the vector path
-  if (!Aligned16(state)) {
-    throw std::invalid_argument("SparseLazyAdamBf16: state must be 16 B-aligned");
-  }
-  if (nrows == 0 || row_len == 0) return;
-  StepArgs a{};
-  a.rows = rows_dev;
-  a.nrows = nrows;
-  a.rec = SparseLazyAdamStateFloats(1, row_len, rowwise);
-  a.row_len = static_cast<float>(row_len);
-  a.lr = lr;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.omb1 = 1.f - beta1;
-  a.omb2 = 1.f - beta2;
-  a.eps = eps;
-  a.shift = key_shift;
-  a.base = row_base;
-  a.tab_rows = table_rows;
-  a.rd = Rounding{seed, rounding == Bf16Rounding::kStochastic};
-  // 8-element units need whole units and table, grad and out on a 16 B
-  // boundary; the records' moments then are, their length being a multiple
-  // of four floats
-  bool vec = row_len % 8 == 0 && Aligned16(table) && Aligned16(grad, out_or_null);
-  LaunchStep<Opt::kLazyAdam>(table, state, grad, out_or_null, row_len, vec, rowwise, a, grid_cap,
-                             s);
+  LazyAdam(table, state, grad, out_or_null, lr, beta1, beta2, eps,
+           StepCall{"SparseLazyAdamBf16", rows_dev, nrows, row_len, rowwise, rounding, seed, s,
+                    key_shift, row_base, table_rows, grid_cap});
+}
+void SparseLazyAdamBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
+                            size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
+                            float beta1, float beta2, float eps, bool rowwise,
+                            Bf16Rounding rounding, uint64_t seed, hipStream_t s, int key_shift,
+                            uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  LazyAdam(table, state, grad, out_or_null, lr, beta1, beta2, eps,
+           StepCall{"SparseLazyAdamBf16Wire", rows_dev, nrows, row_len, rowwise, rounding, seed, s,
+                    key_shift, row_base, table_rows, grid_cap});
 }
 
 }  // namespace kern

@@ -3,7 +3,8 @@
 // occurrence to the sorted unique keys, one summed row per key and, for
 // every occurrence, the slot of its key. The sums add a key's rows in
 // ascending occurrence index, one IEEE fp32 add each, so the message is a
-// function of the inputs alone.
+// function of the inputs alone. The sums leave as fp32, or for a 16-bit wire
+// as bf16 bits: the same fp32 sum, rounded once to nearest even on the store.
 //
 // Tile size: kTile = 1024 elements, 4 per lane of a 256-lane block; key and
 // occurrence index sit in LDS as two arrays (8 B + 4 B per element), 12 KB
@@ -329,18 +330,47 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+struct Float8 {
+  float4 lo, hi;
+};
 __device__ inline float Add(float a, float b) { return a + b; }
 __device__ inline float4 Add(float4 a, float4 b) {
   return float4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
+}
+__device__ inline Float8 Add(Float8 a, Float8 b) {
+  return Float8{Add(a.lo, b.lo), Add(a.hi, b.hi)};
+}
+
+// round-to-nearest-even to bf16 bits, sparse_bf16.hip's nearest rule: Inf as
+// it is, a NaN keeps a mantissa bit
+__device__ inline uint32_t Bf16(float x) {
+  const uint32_t u = __float_as_uint(x);
+  uint32_t h = u >> 16;
+  if ((u & 0x7f800000u) == 0x7f800000u) {
+    if ((h & 0x7fu) == 0 && (u & 0xffffu)) h |= 0x40u;
+    return h;
+  }
+  return (u + 0x7fffu + (h & 1u)) >> 16;
+}
+__device__ inline uint32_t Bf16x2(float a, float b) { return Bf16(a) | (Bf16(b) << 16); }
+
+// a row sum on its way out: as it is, or as bf16 bits (8 of them: one 16 B store)
+__device__ inline void Put(float* p, float v) { *p = v; }
+__device__ inline void Put(float4* p, float4 v) { *p = v; }
+__device__ inline void Put(uint16_t* p, float v) { *p = static_cast<uint16_t>(Bf16(v)); }
+__device__ inline void Put(uint4* p, Float8 v) {
+  *p = uint4{Bf16x2(v.lo.x, v.lo.y), Bf16x2(v.lo.z, v.lo.w), Bf16x2(v.hi.x, v.hi.y),
+             Bf16x2(v.hi.z, v.hi.w)};
 }
 
 // sums[slot] = +0.0 + grad[i] over the slot's occurrences i < grad_rows in
 // ascending i. A group of G = 1 << log2g lanes owns a slot and walks its
 // segment of the sorted index array once per G vectors of the row; the
 // rows of kAhead occurrences are in flight before the first of their adds.
-template <class V>
+// V is a lane's vector of the gradient, S what it stores of the sums.
+template <class V, class S>
 __global__ void __launch_bounds__(kBlock)
-    coalesce_row_sums(const V* __restrict__ grad, V* __restrict__ sums,
+    coalesce_row_sums(const V* __restrict__ grad, S* __restrict__ sums,
                       const uint32_t* __restrict__ seg, const uint32_t* __restrict__ order,
                       const uint32_t* __restrict__ m_dev, uint32_t grad_rows, size_t nv,
                       int log2g) {
@@ -379,13 +409,13 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
         for (int k = 0; k < kAhead; ++k) i[k] = next[k];
       }
-      sums[slot * nv + c] = acc;
+      Put(sums + slot * nv + c, acc);
     }
   }
 }
 
-template <class V>
-void LaunchRowSums(const float* grad, float* sums, const uint32_t* seg, const uint32_t* order,
+template <class V, class S, class T>
+void LaunchRowSums(const float* grad, T* sums, const uint32_t* seg, const uint32_t* order,
                    const uint32_t* m_dev, size_t n, size_t grad_rows, size_t nv, int grid_cap,
                    hipStream_t s) {
   int log2g = 0;
@@ -394,8 +424,8 @@ void LaunchRowSums(const float* grad, float* sums, const uint32_t* seg, const ui
   size_t per_wave = 64 >> log2g;
   size_t waves = (n + per_wave - 1) / per_wave;
   int grid = GridFor(waves * 64, 16384, grid_cap);
-  hipLaunchKernelGGL((coalesce_row_sums<V>), dim3(grid), dim3(kBlock), 0, s,
-                     reinterpret_cast<const V*>(grad), reinterpret_cast<V*>(sums), seg, order,
+  hipLaunchKernelGGL((coalesce_row_sums<V, S>), dim3(grid), dim3(kBlock), 0, s,
+                     reinterpret_cast<const V*>(grad), reinterpret_cast<S*>(sums), seg, order,
                      m_dev, static_cast<uint32_t>(grad_rows), nv, log2g);
 }
 
@@ -431,6 +461,29 @@ inline bool Aligned8(const Ptrs*... p) {
   return ((reinterpret_cast<uintptr_t>(p) | ...) & 7u) == 0;
 }
 
+// the row sums of a coalesced message, in the widest vectors the call admits
+void RowSums(const float* grad, float* sums, const Workspace& w, const uint32_t* order, size_t n,
+             size_t with_grad, size_t row_len, int grid_cap, hipStream_t s) {
+  // float4 needs whole vectors and both arrays on a 16 B boundary
+  if (row_len % 4 == 0 && Aligned16(grad, sums)) {
+    LaunchRowSums<float4, float4>(grad, sums, w.seg, order, w.m, n, with_grad, row_len / 4,
+                                  grid_cap, s);
+  } else {
+    LaunchRowSums<float, float>(grad, sums, w.seg, order, w.m, n, with_grad, row_len, grid_cap, s);
+  }
+}
+void RowSums(const float* grad, uint16_t* sums, const Workspace& w, const uint32_t* order, size_t n,
+             size_t with_grad, size_t row_len, int grid_cap, hipStream_t s) {
+  // 8 sums are one 16 B store: whole units and both arrays on a 16 B boundary
+  if (row_len % 8 == 0 && Aligned16(grad) && Aligned16(sums)) {
+    LaunchRowSums<Float8, uint4>(grad, sums, w.seg, order, w.m, n, with_grad, row_len / 8,
+                                 grid_cap, s);
+  } else {
+    LaunchRowSums<float, uint16_t>(grad, sums, w.seg, order, w.m, n, with_grad, row_len, grid_cap,
+                                   s);
+  }
+}
+
 }  // namespace
 
 int SparseCoalesceTile() { return kTile; }
@@ -439,10 +492,13 @@ size_t SparseCoalesceWorkspaceBytes(size_t n) {
   return Workspace(0, n).bytes + 16;  // the caller's pointer may sit anywhere in 16 B
 }
 
-size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const float* grad_or_null,
-                      size_t grad_rows, size_t row_len, uint64_t* uniq_keys, float* sums_or_null,
-                      int64_t* inverse, void* workspace, size_t workspace_bytes, hipStream_t s,
-                      int grid_cap) {
+namespace {
+
+template <class T>
+size_t Coalesce(const uint64_t* ids_dev, size_t n, int key_shift, const float* grad_or_null,
+                size_t grad_rows, size_t row_len, uint64_t* uniq_keys, T* sums_or_null,
+                int64_t* inverse, void* workspace, size_t workspace_bytes, hipStream_t s,
+                int grid_cap) {
   if (n >= (size_t{1} << 31)) throw std::invalid_argument("SparseCoalesce: n must be below 2^31");
   if (grad_rows > n) throw std::invalid_argument("SparseCoalesce: grad_rows exceeds n");
   if (grad_or_null && row_len == 0) {
@@ -487,15 +543,8 @@ size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const fl
                        w.tile_heads, emit);
   }
   if (sums_or_null && row_len) {
-    const size_t with_grad = grad_or_null ? grad_rows : 0;
-    // float4 needs whole vectors and both arrays on a 16 B boundary
-    if (row_len % 4 == 0 && Aligned16(grad_or_null, sums_or_null)) {
-      LaunchRowSums<float4>(grad_or_null, sums_or_null, w.seg, order, w.m, n, with_grad,
-                            row_len / 4, grid_cap, s);
-    } else {
-      LaunchRowSums<float>(grad_or_null, sums_or_null, w.seg, order, w.m, n, with_grad, row_len,
-                           grid_cap, s);
-    }
+    RowSums(grad_or_null, sums_or_null, w, order, n, grad_or_null ? grad_rows : 0, row_len,
+            grid_cap, s);
   }
   uint32_t m = 0;
   hipError_t e = hipMemcpyAsync(&m, w.m, sizeof(m), hipMemcpyDeviceToHost, s);
@@ -504,6 +553,23 @@ size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const fl
     throw std::runtime_error(std::string("SparseCoalesce: ") + hipGetErrorString(e));
   }
   return m;
+}
+
+}  // namespace
+
+size_t SparseCoalesce(const uint64_t* ids_dev, size_t n, int key_shift, const float* grad_or_null,
+                      size_t grad_rows, size_t row_len, uint64_t* uniq_keys, float* sums_or_null,
+                      int64_t* inverse, void* workspace, size_t workspace_bytes, hipStream_t s,
+                      int grid_cap) {
+  return Coalesce(ids_dev, n, key_shift, grad_or_null, grad_rows, row_len, uniq_keys, sums_or_null,
+                  inverse, workspace, workspace_bytes, s, grid_cap);
+}
+size_t SparseCoalesceBf16(const uint64_t* ids_dev, size_t n, int key_shift,
+                          const float* grad_or_null, size_t grad_rows, size_t row_len,
+                          uint64_t* uniq_keys, uint16_t* sums_or_null, int64_t* inverse,
+                          void* workspace, size_t workspace_bytes, hipStream_t s, int grid_cap) {
+  return Coalesce(ids_dev, n, key_shift, grad_or_null, grad_rows, row_len, uniq_keys, sums_or_null,
+                  inverse, workspace, workspace_bytes, s, grid_cap);
 }
 
 }  // namespace kern

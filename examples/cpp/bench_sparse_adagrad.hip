@@ -5,9 +5,10 @@
 // Python.
 //
 //   build/bench_sparse_adagrad [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16]
+//                              [--row-len L]
 //
 // Shape: the sparse bench config, a 1M x 64 fp32 table with 8192 unique
-// rows per step. Two key schedules: "hot", the same 8192 rows every step
+// rows per step; --row-len sets another row length, a multiple of 8. Two key schedules: "hot", the same 8192 rows every step
 // (what the bench does: the rows stay in cache), and "rotating", 64
 // disjoint sets of 8192 rows taken in turn (128 MiB of table rows between
 // two visits of a set). Every round times, each between its own pair of
@@ -23,6 +24,8 @@
 //   adagrad / adagrad16   row-wise Adagrad step with out
 //   adam / adam16         row-wise lazy Adam step with out
 //   gather / gather16     SparseGatherF32 / SparseGatherBf16
+// and after each bf16-table kernel its 16-bit-wire sibling (adagrad16w,
+// adam16w, gather16w: bf16 gradient in, bf16 rows out) on the same keys.
 // Output: median, 10th and 90th percentile of each in microseconds.
 #include <hip/hip_runtime.h>
 
@@ -45,7 +48,8 @@
 
 namespace {
 
-constexpr size_t kRows = 1u << 20, kRowLen = 64, kHot = 8192, kSets = 64;
+constexpr size_t kRows = 1u << 20, kHot = 8192, kSets = 64;
+size_t g_row_len = 64;  // --row-len
 
 __global__ void fill_kernel(float* p, size_t n, unsigned salt, float scale) {
   size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
@@ -55,6 +59,13 @@ __global__ void fill_kernel(float* p, size_t n, unsigned salt, float scale) {
     x ^= x >> 15;
     p[i] = scale * static_cast<float>(static_cast<int>(x & 0xffffu) - 32768) / 32768.0f;
   }
+}
+
+// the upper halves of n floats: bf16 bits, truncated
+__global__ void narrow_kernel(uint16_t* dst, const float* src, size_t n) {
+  size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (; i < n; i += stride) dst[i] = static_cast<uint16_t>(__float_as_uint(src[i]) >> 16);
 }
 
 // fresh lazy-Adam records of rec floats: p1 = p2 = 1, the rest +0.0
@@ -67,7 +78,7 @@ __global__ void fresh_kernel(float* p, size_t n, size_t rec) {
 void Report(const char* schedule, const char* name, std::vector<float>* us) {
   std::sort(us->begin(), us->end());
   size_t n = us->size();
-  printf("%-9s %-9s %9.2f %9.2f %9.2f\n", schedule, name, (*us)[n / 2], (*us)[n / 10],
+  printf("%-9s %-10s %9.2f %9.2f %9.2f\n", schedule, name, (*us)[n / 2], (*us)[n / 10],
          (*us)[n * 9 / 10]);
 }
 
@@ -88,7 +99,7 @@ float TimeUs(hipEvent_t e0, hipEvent_t e1, Fn fn) {
 // turn away, as the pair does in the default mode
 void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* grad, float* out,
                 const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
-  size_t nstate = xps::kern::SparseLazyAdamStateFloats(kRows, kRowLen, rowwise);
+  size_t nstate = xps::kern::SparseLazyAdamStateFloats(kRows, g_row_len, rowwise);
   float* records;
   CHECK(hipMalloc(reinterpret_cast<void**>(&records), nstate * 4));
   hipLaunchKernelGGL(fresh_kernel, dim3(4096), dim3(256), 0, nullptr, records, nstate,
@@ -100,13 +111,13 @@ void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* gra
       size_t turn = static_cast<size_t>(r + 20);
       const uint64_t* k = keys + (rotating ? (turn % kSets) * kHot : 0);
       float us = TimeUs(e0, e1, [&] {
-        xps::kern::SparseLazyAdamF32(table, records, k, kHot, kRowLen, grad, out, 0.01f, 0.9f,
+        xps::kern::SparseLazyAdamF32(table, records, k, kHot, g_row_len, grad, out, 0.01f, 0.9f,
                                      0.999f, 1e-8f, rowwise, nullptr, 0, 0, kRows);
       });
       if (r >= 0) us_adam.push_back(us);
       if (rotating) k = keys + ((turn + kSets / 2) % kSets) * kHot;
       us = TimeUs(e0, e1, [&] {
-        xps::kern::SparseAdagradF32(table, state, k, kHot, kRowLen, grad, out, 0.01f, 1e-8f,
+        xps::kern::SparseAdagradF32(table, state, k, kHot, g_row_len, grad, out, 0.01f, 1e-8f,
                                     /*rowwise=*/true, nullptr, 0, 0, kRows);
       });
       if (r >= 0) us_adagrad.push_back(us);
@@ -118,18 +129,23 @@ void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* gra
   CHECK(hipFree(records));
 }
 
-// --bf16: each bf16-table kernel beside its fp32 sibling. Both tables see
-// the same keys; the two lazy-Adam launches share one set of records and the
-// two Adagrad launches one state, which only the timing reads.
+// --bf16: each bf16-table kernel beside its fp32 sibling and its 16-bit-wire
+// sibling. Both tables see the same keys; the lazy-Adam launches share one
+// set of records and the Adagrad launches one state, which only the timing
+// reads. The 16-bit wire reads the gradient's upper halves and writes out16.
 void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
                 const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
   namespace k = xps::kern;
   const auto kSr = k::Bf16Rounding::kStochastic;
-  size_t nstate = k::SparseLazyAdamStateFloats(kRows, kRowLen, true);
+  size_t nstate = k::SparseLazyAdamStateFloats(kRows, g_row_len, true);
   float* records;
-  uint16_t* table16;
+  uint16_t *table16, *grad16, *out16;
   CHECK(hipMalloc(reinterpret_cast<void**>(&records), nstate * 4));
-  CHECK(hipMalloc(reinterpret_cast<void**>(&table16), kRows * kRowLen * 2));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&table16), kRows * g_row_len * 2));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&grad16), kHot * g_row_len * 2));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&out16), kHot * g_row_len * 2));
+  hipLaunchKernelGGL(narrow_kernel, dim3(64), dim3(256), 0, nullptr, grad16, grad,
+                     kHot * g_row_len);
   hipLaunchKernelGGL(fresh_kernel, dim3(4096), dim3(256), 0, nullptr, records, nstate,
                      nstate / kRows);
   // the bf16 table starts as the fp32 table, rounded to nearest
@@ -138,47 +154,61 @@ void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
   uint64_t* all;
   CHECK(hipMalloc(reinterpret_cast<void**>(&all), kRows * 8));
   CHECK(hipMemcpy(all, h.data(), kRows * 8, hipMemcpyHostToDevice));
-  k::SparseScatterAssignBf16(table16, all, kRows, kRowLen, table, nullptr, 0, 0, kRows);
+  k::SparseScatterAssignBf16(table16, all, kRows, g_row_len, table, nullptr, 0, 0, kRows);
   CHECK(hipDeviceSynchronize());
   CHECK(hipFree(all));
   for (int rotating = 0; rotating < 2; ++rotating) {
-    std::vector<float> us[6];
+    std::vector<float> us[9];
     for (int r = -20; r < rounds; ++r) {
       size_t turn = static_cast<size_t>(r + 20);
       const uint64_t* kf = keys + (rotating ? ((turn + kSets / 2) % kSets) * kHot : 0);
       const uint64_t* kb = keys + (rotating ? (turn % kSets) * kHot : 0);
       uint64_t seed = turn;
-      float t[6];
+      float t[9];
       t[0] = TimeUs(e0, e1, [&] {
-        k::SparseAdagradF32(table, state, kf, kHot, kRowLen, grad, out, 0.01f, 1e-8f, true,
+        k::SparseAdagradF32(table, state, kf, kHot, g_row_len, grad, out, 0.01f, 1e-8f, true,
                             nullptr, 0, 0, kRows);
       });
       t[1] = TimeUs(e0, e1, [&] {
-        k::SparseAdagradBf16(table16, state, kb, kHot, kRowLen, grad, out, 0.01f, 1e-8f, true, kSr,
+        k::SparseAdagradBf16(table16, state, kb, kHot, g_row_len, grad, out, 0.01f, 1e-8f, true, kSr,
                              seed, nullptr, 0, 0, kRows);
       });
       t[2] = TimeUs(e0, e1, [&] {
-        k::SparseLazyAdamF32(table, records, kf, kHot, kRowLen, grad, out, 0.01f, 0.9f, 0.999f,
-                             1e-8f, true, nullptr, 0, 0, kRows);
+        k::SparseAdagradBf16Wire(table16, state, kb, kHot, g_row_len, grad16, out16, 0.01f, 1e-8f,
+                                 true, kSr, seed, nullptr, 0, 0, kRows);
       });
       t[3] = TimeUs(e0, e1, [&] {
-        k::SparseLazyAdamBf16(table16, records, kb, kHot, kRowLen, grad, out, 0.01f, 0.9f, 0.999f,
-                              1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
+        k::SparseLazyAdamF32(table, records, kf, kHot, g_row_len, grad, out, 0.01f, 0.9f, 0.999f,
+                             1e-8f, true, nullptr, 0, 0, kRows);
       });
       t[4] = TimeUs(e0, e1, [&] {
-        k::SparseGatherF32(table, kf, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+        k::SparseLazyAdamBf16(table16, records, kb, kHot, g_row_len, grad, out, 0.01f, 0.9f, 0.999f,
+                              1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
       });
       t[5] = TimeUs(e0, e1, [&] {
-        k::SparseGatherBf16(table16, kb, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+        k::SparseLazyAdamBf16Wire(table16, records, kb, kHot, g_row_len, grad16, out16, 0.01f, 0.9f,
+                                  0.999f, 1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
       });
-      for (int i = 0; i < 6 && r >= 0; ++i) us[i].push_back(t[i]);
+      t[6] = TimeUs(e0, e1, [&] {
+        k::SparseGatherF32(table, kf, kHot, g_row_len, out, nullptr, 0, 0, kRows);
+      });
+      t[7] = TimeUs(e0, e1, [&] {
+        k::SparseGatherBf16(table16, kb, kHot, g_row_len, out, nullptr, 0, 0, kRows);
+      });
+      t[8] = TimeUs(e0, e1, [&] {
+        k::SparseGatherBf16Wire(table16, kb, kHot, g_row_len, out16, nullptr, 0, 0, kRows);
+      });
+      for (int i = 0; i < 9 && r >= 0; ++i) us[i].push_back(t[i]);
     }
     CHECK(hipGetLastError());
-    const char* names[6] = {"adagrad", "adagrad16", "adam", "adam16", "gather", "gather16"};
-    for (int i = 0; i < 6; ++i) Report(rotating ? "rotating" : "hot", names[i], &us[i]);
+    const char* names[9] = {"adagrad", "adagrad16", "adagrad16w", "adam",     "adam16",
+                            "adam16w", "gather",    "gather16",   "gather16w"};
+    for (int i = 0; i < 9; ++i) Report(rotating ? "rotating" : "hot", names[i], &us[i]);
   }
   CHECK(hipFree(records));
   CHECK(hipFree(table16));
+  CHECK(hipFree(grad16));
+  CHECK(hipFree(out16));
 }
 
 }  // namespace
@@ -195,24 +225,27 @@ int main(int argc, char** argv) {
       opt = argv[++i];
     } else if (!strcmp(argv[i], "--bf16")) {
       bf16 = true;
+    } else if (!strcmp(argv[i], "--row-len") && i + 1 < argc) {
+      g_row_len = static_cast<size_t>(atoi(argv[++i]));
     } else {
-      fprintf(stderr, "usage: %s [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16]\n",
+      fprintf(stderr,
+              "usage: %s [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16] [--row-len L]\n",
               argv[0]);
       return 2;
     }
   }
-  if (rounds < 10) return 2;
+  if (rounds < 10 || g_row_len == 0 || g_row_len % 8 || g_row_len > 4096) return 2;
 
   float *table, *state, *grad, *out;
   uint64_t* keys;
-  CHECK(hipMalloc(reinterpret_cast<void**>(&table), kRows * kRowLen * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&table), kRows * g_row_len * 4));
   CHECK(hipMalloc(reinterpret_cast<void**>(&state), kRows * 4));
-  CHECK(hipMalloc(reinterpret_cast<void**>(&grad), kHot * kRowLen * 4));
-  CHECK(hipMalloc(reinterpret_cast<void**>(&out), kHot * kRowLen * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&grad), kHot * g_row_len * 4));
+  CHECK(hipMalloc(reinterpret_cast<void**>(&out), kHot * g_row_len * 4));
   CHECK(hipMalloc(reinterpret_cast<void**>(&keys), kSets * kHot * 8));
-  hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, nullptr, table, kRows * kRowLen, 1u,
+  hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, nullptr, table, kRows * g_row_len, 1u,
                      1.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, nullptr, grad, kHot * kRowLen, 2u, 1e-3f);
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, nullptr, grad, kHot * g_row_len, 2u, 1e-3f);
   CHECK(hipMemset(state, 0, kRows * 4));
   // an odd multiplier permutes the 2^20 rows: the sets are disjoint and
   // every row of a set is unique
@@ -224,9 +257,9 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
-  printf("# %zu x %zu table, %zu rows per step, %d rounds, microseconds\n", kRows, kRowLen, kHot,
+  printf("# %zu x %zu table, %zu rows per step, %d rounds, microseconds\n", kRows, g_row_len, kHot,
          rounds);
-  printf("%-9s %-9s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
+  printf("%-9s %-10s %9s %9s %9s\n", "schedule", "kernel", "median", "p10", "p90");
   if (bf16) {
     Bf16Rounds(rounds, table, state, grad, out, keys, e0, e1);
     return 0;
@@ -241,7 +274,7 @@ int main(int argc, char** argv) {
       const uint64_t* k = keys + (rotating ? (static_cast<size_t>(r + 20) % kSets) * kHot : 0);
       float ms = 0;
       CHECK(hipEventRecord(e0, nullptr));
-      xps::kern::SparseAdagradF32(table, state, k, kHot, kRowLen, grad, out, 0.01f, 1e-8f,
+      xps::kern::SparseAdagradF32(table, state, k, kHot, g_row_len, grad, out, 0.01f, 1e-8f,
                                   /*rowwise=*/true, nullptr, 0, 0, kRows);
       CHECK(hipEventRecord(e1, nullptr));
       CHECK(hipEventSynchronize(e1));
@@ -251,9 +284,9 @@ int main(int argc, char** argv) {
       // launch found its own
       if (rotating) k = keys + (static_cast<size_t>(r + 20 + kSets / 2) % kSets) * kHot;
       CHECK(hipEventRecord(e0, nullptr));
-      xps::kern::SparseScatterAddF32(table, k, kHot, kRowLen, grad, /*atomic=*/false, nullptr, 0,
+      xps::kern::SparseScatterAddF32(table, k, kHot, g_row_len, grad, /*atomic=*/false, nullptr, 0,
                                      0, kRows);
-      xps::kern::SparseGatherF32(table, k, kHot, kRowLen, out, nullptr, 0, 0, kRows);
+      xps::kern::SparseGatherF32(table, k, kHot, g_row_len, out, nullptr, 0, 0, kRows);
       CHECK(hipEventRecord(e1, nullptr));
       CHECK(hipEventSynchronize(e1));
       CHECK(hipEventElapsedTime(&ms, e0, e1));

@@ -17,9 +17,12 @@ per-occurrence rows.
 
 Needs one MI355X.  Run:  python examples/python/train_embedding.py
                         [--optimizer rowwise_adagrad|adagrad|lazy_adam|rowwise_lazy_adam]
-                        [--table-dtype f32|bf16]
+                        [--table-dtype f32|bf16] [--wire-dtype f32|bf16]
 --table-dtype bf16 keeps the table in bf16 (half the bytes per row) with
-stochastic rounding on every store; the messages stay fp32.
+stochastic rounding on every store; the messages stay fp32 unless
+--wire-dtype bf16 (needs the bf16 table) halves them too: sparse_coalesce
+rounds the summed gradients into the pushed tensor, the response is the
+table's bf16 rows, and sparse_gather widens them per occurrence.
 """
 import argparse
 import sys
@@ -43,7 +46,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--optimizer", default="rowwise_adagrad", choices=sorted(LR))
     ap.add_argument("--table-dtype", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--wire-dtype", default="f32", choices=["f32", "bf16"])
     args = ap.parse_args()
+    if args.wire_dtype == "bf16" and args.table_dtype != "bf16":
+        ap.error("--wire-dtype bf16 needs --table-dtype bf16")
     optimizer = args.optimizer
     ps.setup_env(1, 1, root_port=9310, XPS_DEV_ID=0, XPS_POOL_GB=1)
     roles = (("scheduler", -1), ("joint", 0))
@@ -52,14 +58,18 @@ def main():
     [t.join() for t in ths]
     server = ps.KVServer(0)
     server.set_gpu_sparse_handle(ROWS, DIM, optimizer=optimizer, lr=LR[optimizer], eps=1e-8,
-                                 table_dtype=args.table_dtype)
+                                 table_dtype=args.table_dtype, wire_dtype=args.wire_dtype)
     worker = ps.KVWorker(0, 0)
 
     gen = torch.Generator().manual_seed(3)
     hidden = torch.randn(ROWS, DIM, generator=gen).cuda()
     bags = torch.randint(0, ROWS, (STEPS + 1, BATCH, BAG), generator=gen).cuda()
     cap = 2 * BATCH * BAG  # rows of two batches at the most
-    vals, out = ps.pool_tensor((cap, DIM)), ps.pool_tensor((cap, DIM))
+    wire16 = args.wire_dtype == "bf16"
+    pool = [ps.pool_tensor((cap, DIM), "int16" if wire16 else "float32") for _ in range(2)]
+    # a 16-bit wire: bf16 views of pool tensors of half the bytes (`pool` keeps them alive)
+    vals, out = (p.view(torch.bfloat16) for p in pool) if wire16 else pool
+    row_bytes = DIM * vals.element_size()
 
     keys_buf = torch.empty(cap, dtype=torch.int64, device="cuda")
     scratch = torch.empty(ps._core.sparse_coalesce_workspace_bytes(cap), dtype=torch.uint8,
@@ -70,8 +80,8 @@ def main():
         n = ids.numel()
         torch.cuda.synchronize()
         keys = ids.cpu().numpy().astype(np.uint64)
-        lens = np.full(n, DIM, dtype=np.int32)
-        worker.wait(worker.zpushpull_ptr(keys, vals.data_ptr(), out.data_ptr(), n * DIM * 4, 0,
+        lens = np.full(n, row_bytes // 4, dtype=np.int32)  # lens count floats
+        worker.wait(worker.zpushpull_ptr(keys, vals.data_ptr(), out.data_ptr(), n * row_bytes, 0,
                                          lens, cmd=cmd))
         return out[:n].clone()
 
@@ -100,8 +110,8 @@ def main():
     [t.start() for t in ths]
     [t.join() for t in ths]
     assert losses[-1] < 0.5 * losses[0], "the loss did not fall"
-    print("loss %.4f -> %.4f with %s on the server, %s table"
-          % (losses[0], losses[-1], optimizer, args.table_dtype))
+    print("loss %.4f -> %.4f with %s on the server, %s table, %s wire"
+          % (losses[0], losses[-1], optimizer, args.table_dtype, args.wire_dtype))
 
 
 if __name__ == "__main__":

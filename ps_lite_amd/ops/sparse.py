@@ -4,16 +4,20 @@ from .. import _core
 
 
 def sparse_gather(table, rows, out=None):
-    """out[i] = table[rows[i]] for a 2-D fp32 table; rows int64/uint64."""
+    """out[i] = table[rows[i]] for a 2-D fp32 table; rows int64/uint64.
+
+    A torch.bfloat16 table gives fp32 rows, widened exactly: how the rows of
+    a 16-bit pull response become one fp32 row per occurrence."""
     import torch
 
     assert table.is_cuda and table.dim() == 2 and table.is_contiguous()
     assert rows.is_cuda and rows.dim() == 1
     if out is None:
         out = torch.empty(rows.numel(), table.shape[1], device=table.device,
-                          dtype=table.dtype)
-    _core.k_sparse_gather_f32(table.data_ptr(), rows.data_ptr(), rows.numel(),
-                              table.shape[1], out.data_ptr())
+                          dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    gather = _core.k_sparse_gather_bf16 if _is_bf16(table) else _core.k_sparse_gather_f32
+    gather(table.data_ptr(), rows.data_ptr(), rows.numel(), table.shape[1], out.data_ptr())
     return out
 
 
@@ -26,7 +30,8 @@ def sparse_scatter_add(table, rows, src, atomic=False):
     return table
 
 
-def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, workspace=None):
+def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, workspace=None,
+                    sums_dtype=None):
     """Sorted unique keys, summed gradient rows and the slot of every id.
 
     ids: int64 or uint64 CUDA tensor of any shape, any order, any repetition
@@ -37,7 +42,10 @@ def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, w
     bit the same on every run; inverse int64 with inverse[i] the slot of id i.
     out_keys (>= n elements), out_sums (>= n rows of row_len) and workspace
     (>= _core.sparse_coalesce_workspace_bytes(n) bytes) are optional
-    preallocated buffers; with all three nothing but inverse is allocated."""
+    preallocated buffers; with all three nothing but inverse is allocated.
+    A torch.bfloat16 out_sums, or sums_dtype=torch.bfloat16 without one,
+    gives each fp32 sum rounded once to nearest even: the rows a handler with
+    wire_dtype="bf16" takes."""
     import torch
 
     assert ids.is_cuda and ids.dtype in (torch.int64, torch.uint64)
@@ -47,8 +55,10 @@ def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, w
     if grad is not None:
         assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous()
         if out_sums is None:
-            out_sums = torch.empty(n, row_len, device=ids.device, dtype=torch.float32)
-        assert out_sums.is_contiguous() and out_sums.dtype == torch.float32
+            out_sums = torch.empty(n, row_len, device=ids.device,
+                                   dtype=sums_dtype or torch.float32)
+        assert out_sums.is_contiguous() and out_sums.dtype in (torch.float32, torch.bfloat16)
+        assert sums_dtype in (None, out_sums.dtype)
         assert out_sums.dim() == 2 and out_sums.shape[0] >= n and out_sums.shape[1] == row_len
     if out_keys is None:
         out_keys = torch.empty(n, device=ids.device, dtype=ids.dtype)
@@ -61,7 +71,8 @@ def sparse_coalesce(ids, grad=None, key_shift=0, out_keys=None, out_sums=None, w
     m = _core.k_sparse_coalesce(ids.data_ptr(), n, key_shift,
                                 0 if grad is None else grad.data_ptr(), grad_rows, row_len,
                                 out_keys.data_ptr(), 0 if grad is None else out_sums.data_ptr(),
-                                inverse.data_ptr(), workspace.data_ptr(), ws_bytes)
+                                inverse.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                sums_bf16=grad is not None and _is_bf16(out_sums))
     return out_keys[:m], (None if grad is None else out_sums[:m]), inverse
 
 
