@@ -17,8 +17,11 @@ __device__ inline float Step(float w, float g, float lr, float denom) {
 __device__ inline float Denom(float s, float eps) { return sqrtf(s) + eps; }
 
 // Lazy Adam. beta * old + omb * x: both moments, the row-wise second one
-// included
+// included. Two rounded products and their rounded sum: left to the compiler,
+// either product may be fused into the add, and the two files' kernels chose
+// differently (a last-bit difference in m' and v'), so contraction is off here
 __device__ inline float Moment(float old, float x, float beta, float omb) {
+#pragma clang fp contract(off)
   return beta * old + omb * x;
 }
 __device__ inline float AdamDenom(float v, float c2, float eps) { return sqrtf(v / c2) + eps; }

@@ -179,9 +179,10 @@ void LaunchAdagrad(float* table, float* state, const float* grad, float* out, Ad
 
 // ------------------------------------------------------------ lazy Adam
 //
-// The exact order of the fp32 operations, one IEEE rounding each unless the
-// compiler contracts a multiply with the add or subtract that consumes it
-// (the tests' bound counts the uncontracted roundings and holds for both).
+// The exact order of the fp32 operations, one IEEE rounding each. The
+// moments' multiply-adds are compiled uncontracted (sparse_elem.h); the one
+// product left next to a subtraction is p' in 1 - p', where the compiler may
+// use the unrounded p * beta (the tests' bound allows for both).
 // omb1 and omb2 are the fp32 values of 1 - beta1 and 1 - beta2, formed on
 // the host.
 //   per row, by the group's first lane:
