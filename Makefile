@@ -48,9 +48,8 @@ build/%.hip.o: %.hip csrc/*.h
 
 # the optimizer kernels keep fp32 operations unpaired: every multiply, add
 # and divide rounds once, as their error bound counts them
-build/csrc/sparse_opt.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
-# the bf16-table steps run the same operations and round once more on the store
-build/csrc/sparse_bf16.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (a bf16 table's steps run the same operations and round once more on the store)
+build/csrc/sparse_table.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # the coalescer's row sums likewise: one unpaired IEEE add per occurrence
 build/csrc/sparse_coalesce.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
@@ -95,16 +94,15 @@ mxfp8bench: build/csrc/kernels.hip.o build/csrc/mxfp8.hip.o build/bench_mxfp8.o
 
 # one-process timing of the fused Adagrad step against scatter-add + gather,
 # or with --opt of a lazy-Adam step against the Adagrad step (links
-# kernels.hip, sparse_opt.hip and sparse_bf16.hip only; --bf16 times the
+# kernels.hip and sparse_table.hip only; --bf16 times the
 # bf16-table kernels, fp32 and 16-bit wire, beside their fp32 siblings):
 # build/bench_sparse_adagrad
 build/bench_sparse_adagrad.o: examples/cpp/bench_sparse_adagrad.hip csrc/*.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) -c examples/cpp/bench_sparse_adagrad.hip -o build/bench_sparse_adagrad.o
-adagradbench: build/csrc/kernels.hip.o build/csrc/sparse_opt.hip.o build/csrc/sparse_bf16.hip.o \
-    build/bench_sparse_adagrad.o
+adagradbench: build/csrc/kernels.hip.o build/csrc/sparse_table.hip.o build/bench_sparse_adagrad.o
 	$(HIPCC) $(CPPBENCH_LD) build/bench_sparse_adagrad.o build/csrc/kernels.hip.o \
-	    build/csrc/sparse_opt.hip.o build/csrc/sparse_bf16.hip.o -o build/bench_sparse_adagrad
+	    build/csrc/sparse_table.hip.o -o build/bench_sparse_adagrad
 
 # self-contained lint gate (reference parity: tests/lint.py + make lint)
 lint:

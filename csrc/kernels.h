@@ -46,148 +46,123 @@ void DenseSumF32(float* dst, const float* src, size_t n, hipStream_t s, int grid
 // bandwidth-bound dense path)
 void DenseSumBf16(uint16_t* dst, const uint16_t* src, size_t n, hipStream_t s, int grid_cap = 0);
 void BatchedSumBf16(const struct CopyDesc* descs_host, int n, hipStream_t s, int tile_cap = 0);
-// Sparse ops: local row index = (rows[r] >> key_shift) - row_base, so a
-// server can index its local table shard from globally-sharded keys
-// (key = global_row << key_shift spreads rows over the PS key space).
-// table_rows bounds every decoded row index: out-of-range rows (corrupt
-// or misrouted keys) are skipped by scatters and read as zeros by
-// gathers, never touching memory outside the table. The ~0 default
-// disables the check (trusted keys). grid_cap > 0 caps the grid (tests).
-// out[r][:] = table[row(r)][:] for r in [0, nrows)
-void SparseGatherF32(const float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                     float* out, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
-                     uint64_t table_rows = ~0ull, int grid_cap = 0);
-// table[row(r)][:] += src[r][:]; atomic=true tolerates duplicate rows
-void SparseScatterAddF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                         const float* src, bool atomic, hipStream_t s, int key_shift = 0,
-                         uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
-// table[row(r)][:] = src[r][:]
-void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                            const float* src, hipStream_t s, int key_shift = 0,
-                            uint64_t row_base = 0, uint64_t table_rows = ~0ull,
-                            int grid_cap = 0);
-// Adagrad step on the rows r whose decoded row lies in the table, g = grad[r]
-// (sparse_opt.hip):
-//   rowwise:      state[row]    += sum(g * g) / row_len  (one float per row)
-//   element-wise: state[row][c] += g[c] * g[c]           (the table's shape)
-//   table[row][c] -= lr * g[c] / (sqrt(new state) + eps)
-// With out_or_null set, out[r] receives the new row, or zeros for a row
-// outside the table (what the gather gives); table and state are not
-// touched for such a row. In-range rows of one call must be unique, and
-// table, state, grad and out pairwise disjoint. Rows move as float4 when
-// row_len % 4 == 0 and table, grad, out (and an element-wise state) are
-// 16 B-aligned, else as single floats. lr <= 0 or eps <= 0 is
-// std::invalid_argument and nothing is launched.
-void SparseAdagradF32(float* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                      size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
-                      bool rowwise, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
-                      uint64_t table_rows = ~0ull, int grid_cap = 0);
-// Sparse ("lazy") Adam step on the rows r whose decoded row lies in the
-// table, g = grad[r] (sparse_opt.hip). The bias correction is the row's own:
-// p1, p2 are the running products beta1^t, beta2^t of that row's steps.
-//   p1' = p1 * beta1,  p2' = p2 * beta2
-//   m'  = beta1 * m + (1 - beta1) * g
-//   v'  = beta2 * v + (1 - beta2) * g * g                 (element-wise)
-//   v'  = beta2 * v + (1 - beta2) * sum(g * g) / row_len  (rowwise: one float per row)
-//   w'  = w - (lr / (1 - p1')) * m' / (sqrt(v' / (1 - p2')) + eps)
-// state holds one record per table row,
-//   { p1, p2, v_row, 0 }  m[row_len]  v[row_len] (element-wise only)
-// SparseLazyAdamStateFloats floats in all; a fresh state has p1 = p2 = 1 and
-// +0.0 everywhere else (v_row is unused element-wise). out_or_null, row
-// uniqueness, disjointness and rows outside the table are as for Adagrad.
-// Rows move as float4 when row_len % 4 == 0 and table, grad and out are
-// 16 B-aligned, else as single floats. lr <= 0, eps <= 0, a beta outside
-// [0, 1) or a state off a 16 B boundary is std::invalid_argument and nothing
-// is launched.
-size_t SparseLazyAdamStateFloats(size_t rows, size_t row_len, bool rowwise);
-void SparseLazyAdamF32(float* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                       size_t row_len, const float* grad, float* out_or_null, float lr, float beta1,
-                       float beta2, float eps, bool rowwise, hipStream_t s, int key_shift = 0,
-                       uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
-// The same ops over a bf16 table (sparse_bf16.hip): `table` holds bf16 bits,
-// every other array stays fp32. A weight is widened exactly, the fp32
-// operations are those of the F32 sibling in the same order, and the result
-// x (bits u) is rounded once on the store by R:
+// Sparse ops over an embedding table (sparse_table.hip; the fp32 table's
+// gather, assign and add kernels are kernels.hip's). A call names its rows
+// (SparseRows), its table (SparseTable) and its wire side, the gradients or
+// pushed values in and the rows out (SparseWire); the dtypes are dispatched
+// inside the five entry points. An fp32 table with a bf16 wire, and an atomic
+// add on a bf16 table, have no kernel: std::invalid_argument before any HIP
+// call, like every argument check below.
+enum class SparseDtype { kF32, kBf16 };
+// Which rows a call touches and where it runs. Local row index =
+// (keys[r] >> key_shift) - row_base, so a server can index its local table
+// shard from globally-sharded keys (key = global_row << key_shift spreads
+// rows over the PS key space). table_rows bounds every decoded row index:
+// out-of-range rows (corrupt or misrouted keys) are skipped by scatters and
+// steps and read as zeros by gathers, never touching memory outside the
+// table. The ~0 default disables the check (trusted keys). grid_cap > 0 caps
+// the grid (tests).
+struct SparseRows {
+  const uint64_t* keys;  // device memory
+  size_t nrows;
+  size_t row_len;
+  int key_shift = 0;
+  uint64_t row_base = 0;
+  uint64_t table_rows = ~0ull;
+  hipStream_t s = nullptr;
+  int grid_cap = 0;
+};
+// A bf16 table holds bf16 bits and says how a result x (bits u) is rounded
+// on the store, the rule R:
 //   kNearest:    round-to-nearest-even
 //   kStochastic: (u + r) >> 16, r uniform in [0, 2^16): the magnitude goes up
 //                with probability (u & 0xffff) / 2^16; a bf16 value keeps its bits
 // Inf and NaN pass through both. r is 16 bits of a counter-based generator
 // keyed on (seed, local row, element index) (SplitMix64, stated at the top
-// of sparse_bf16.hip): the same call gives the same table bits under any
-// grid_cap and on either path. Rows move as 8-element units (one 16 B table
-// access against two float4) when row_len % 8 == 0 and the table and the
-// fp32 arrays (an element-wise Adagrad state included) are 16 B-aligned,
-// else element by element for the whole call.
+// of sparse_table.hip): the same call gives the same table bits under any
+// grid_cap and on either path. An fp32 table stores x itself and ignores
+// rounding and seed.
 enum class Bf16Rounding { kNearest, kStochastic };
+struct SparseTable {
+  void* p;
+  SparseDtype dtype;
+  Bf16Rounding rounding = Bf16Rounding::kNearest;
+  uint64_t seed = 0;
+};
+// fp32 values, or for a bf16 table bf16 bits: values in are widened exactly,
+// rows out are the stored bits (0x0000 for a key outside the table). Fed bits
+// b, a step or an add leaves the table and state bits it leaves fed widen(b)
+// on the fp32 wire.
+struct SparseWire {
+  void* p;
+  SparseDtype dtype;
+};
 // the seed of a handler's n-th rounding launch: mix(seed + (n + 1) * phi)
 uint64_t SparseBf16LaunchSeed(uint64_t seed, uint64_t n);
-// out[r][:] = float(table[row(r)][:]), exact; zeros for a key outside the table
-void SparseGatherBf16(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
-                      size_t row_len, float* out, hipStream_t s, int key_shift = 0,
-                      uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
-// table[row(r)][:] = RNE_bf16(src[r][:]): always nearest, no seed (how
-// weights are initialised)
-void SparseScatterAssignBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
-                             size_t row_len, const float* src, hipStream_t s, int key_shift = 0,
-                             uint64_t row_base = 0, uint64_t table_rows = ~0ull,
-                             int grid_cap = 0);
-// table[row(r)][:] = R(float(table[row(r)][:]) + src[r][:]), one fp32 add.
-// Not atomic: in-range rows of one call must be unique, and calls on one
-// table ordered by the caller.
-void SparseScatterAddBf16(uint16_t* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                          const float* src, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
-                          int key_shift = 0, uint64_t row_base = 0, uint64_t table_rows = ~0ull,
-                          int grid_cap = 0);
-// SparseAdagradF32 / SparseLazyAdamF32 with table[row][c] = R(w'): the same
-// state layouts, records, requirements and std::invalid_argument cases. With
-// out_or_null set, out[r][c] is the stored bf16 widened, what a later gather
-// returns bit for bit (not the unrounded w'), or zeros for a row outside the
-// table.
-void SparseAdagradBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                       size_t row_len, const float* grad, float* out_or_null, float lr, float eps,
-                       bool rowwise, Bf16Rounding rounding, uint64_t seed, hipStream_t s,
-                       int key_shift = 0, uint64_t row_base = 0, uint64_t table_rows = ~0ull,
-                       int grid_cap = 0);
-void SparseLazyAdamBf16(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                        size_t row_len, const float* grad, float* out_or_null, float lr,
-                        float beta1, float beta2, float eps, bool rowwise, Bf16Rounding rounding,
-                        uint64_t seed, hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
-                        uint64_t table_rows = ~0ull, int grid_cap = 0);
-// The bf16-table ops with bf16 bits on the wire side too: gradients and
-// pushed values come as bf16 bits and are widened exactly, rows out are the
-// stored bits (0x0000 for a key outside the table). Fed bits b, a step or an
-// add leaves the table and state bits its sibling above leaves fed widen(b).
-// 8-element units (one 16 B access per array) need row_len % 8 == 0 and
-// table, grad/src and out (and an element-wise Adagrad state) 16 B-aligned;
-// else the whole call moves uint16_t against uint16_t. Everything else,
-// the std::invalid_argument cases included, is the sibling's.
-// out[r][:] = table[row(r)][:] as bits
-void SparseGatherBf16Wire(const uint16_t* table, const uint64_t* rows_dev, size_t nrows,
-                          size_t row_len, uint16_t* out, hipStream_t s, int key_shift = 0,
-                          uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
-// table[row(r)][:] = src[r][:] as bits: no rounding, the sender rounded
-void SparseScatterAssignBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
-                                 size_t row_len, const uint16_t* src, hipStream_t s,
-                                 int key_shift = 0, uint64_t row_base = 0,
-                                 uint64_t table_rows = ~0ull, int grid_cap = 0);
-// table[row(r)][c] = R(float(table[row(r)][c]) + float(src[r][c])), one fp32 add
-void SparseScatterAddBf16Wire(uint16_t* table, const uint64_t* rows_dev, size_t nrows,
-                              size_t row_len, const uint16_t* src, Bf16Rounding rounding,
-                              uint64_t seed, hipStream_t s, int key_shift = 0,
-                              uint64_t row_base = 0, uint64_t table_rows = ~0ull,
-                              int grid_cap = 0);
-// SparseAdagradBf16 with g = float(grad bits); out[r][c] = the stored bits
-void SparseAdagradBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                           size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
-                           float eps, bool rowwise, Bf16Rounding rounding, uint64_t seed,
-                           hipStream_t s, int key_shift = 0, uint64_t row_base = 0,
-                           uint64_t table_rows = ~0ull, int grid_cap = 0);
-// SparseLazyAdamBf16 with g = float(grad bits); out[r][c] = the stored bits
-void SparseLazyAdamBf16Wire(uint16_t* table, float* state, const uint64_t* rows_dev, size_t nrows,
-                            size_t row_len, const uint16_t* grad, uint16_t* out_or_null, float lr,
-                            float beta1, float beta2, float eps, bool rowwise,
-                            Bf16Rounding rounding, uint64_t seed, hipStream_t s, int key_shift = 0,
-                            uint64_t row_base = 0, uint64_t table_rows = ~0ull, int grid_cap = 0);
+// How rows move. An fp32 table: as float4 when row_len % 4 == 0 (gather,
+// assign, add), for a step when also table, grad and out (and an
+// element-wise Adagrad state) are 16 B-aligned, else as single floats. A
+// bf16 table: as 8-element units (one 16 B table access against two float4,
+// or against one 16 B access of a bf16 wire) when row_len % 8 == 0 and the
+// table and the wire arrays (and an element-wise Adagrad state) are
+// 16 B-aligned, else element by element for the whole call.
+//
+// out[r][:] = table[row(r)][:] for r in [0, nrows), a bf16 weight widened
+// exactly (bf16 wire: as bits); zeros for a key outside the table
+void SparseGather(const SparseTable& table, const SparseRows& rows, SparseWire out);
+// table[row(r)][:] = src[r][:]. A bf16 table stores RNE_bf16(src): always
+// nearest, no seed (how weights are initialised); from a bf16 wire the bits
+// as they are, the sender rounded.
+void SparseScatterAssign(const SparseTable& table, const SparseRows& rows, SparseWire src);
+// table[row(r)][:] = R(table[row(r)][:] + src[r][:]), one fp32 add.
+// atomic = true (fp32 table only) tolerates duplicate rows; otherwise
+// in-range rows of one call must be unique, and calls on one table ordered by
+// the caller.
+void SparseScatterAdd(const SparseTable& table, const SparseRows& rows, SparseWire src,
+                      bool atomic = false);
+// Adagrad step on the rows r whose decoded row lies in the table, g = grad[r]:
+//   rowwise:      state[row]    += sum(g * g) / row_len  (one float per row)
+//   element-wise: state[row][c] += g[c] * g[c]           (the table's shape)
+//   table[row][c] = R(table[row][c] - lr * g[c] / (sqrt(new state) + eps))
+// The state is fp32 whatever the table; a bf16 weight is widened exactly, the
+// fp32 operations are the fp32 table's in the same order, and the result is
+// rounded once on the store. With out_or_null.p set, out[r] receives the new
+// row as stored, what a later gather returns bit for bit (not the unrounded
+// w'), or zeros for a row outside the table; table and state are not touched
+// for such a row. out is of grad's dtype. In-range rows of one call must be
+// unique, and table, state, grad and out pairwise disjoint. lr <= 0 or
+// eps <= 0 is std::invalid_argument and nothing is launched.
+struct AdagradParams {
+  float lr;
+  float eps;
+  bool rowwise;
+};
+void SparseAdagrad(const SparseTable& table, float* state, const SparseRows& rows,
+                   SparseWire grad, SparseWire out_or_null, const AdagradParams& params);
+// Sparse ("lazy") Adam step on the rows r whose decoded row lies in the
+// table, g = grad[r]. The bias correction is the row's own: p1, p2 are the
+// running products beta1^t, beta2^t of that row's steps.
+//   p1' = p1 * beta1,  p2' = p2 * beta2
+//   m'  = beta1 * m + (1 - beta1) * g
+//   v'  = beta2 * v + (1 - beta2) * g * g                 (element-wise)
+//   v'  = beta2 * v + (1 - beta2) * sum(g * g) / row_len  (rowwise: one float per row)
+//   w'  = R(w - (lr / (1 - p1')) * m' / (sqrt(v' / (1 - p2')) + eps))
+// state holds one record per table row,
+//   { p1, p2, v_row, 0 }  m[row_len]  v[row_len] (element-wise only)
+// SparseLazyAdamStateFloats floats in all; a fresh state has p1 = p2 = 1 and
+// +0.0 everywhere else (v_row is unused element-wise). The table's dtype,
+// out_or_null, row uniqueness, disjointness and rows outside the table are as
+// for Adagrad. lr <= 0, eps <= 0, a beta outside [0, 1) or a state off a
+// 16 B boundary is std::invalid_argument and nothing is launched.
+struct LazyAdamParams {
+  float lr;
+  float beta1, beta2;
+  float eps;
+  bool rowwise;
+};
+size_t SparseLazyAdamStateFloats(size_t rows, size_t row_len, bool rowwise);
+void SparseLazyAdam(const SparseTable& table, float* state, const SparseRows& rows,
+                    SparseWire grad, SparseWire out_or_null, const LazyAdamParams& params);
 // Worker side of the sparse ops (sparse_coalesce.hip): a batch's ids, in any
 // order and with any repetition, become the sorted unique keys the ops above
 // and the handlers want. ids compare as unsigned 64-bit values.

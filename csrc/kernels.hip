@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "sparse_move_f32.h"
 #include "tile_runs.h"
 
 namespace xps {
@@ -470,48 +471,46 @@ static int SparseGrid(size_t work_items, int grid_cap) {
   return GridFor(work_items, 16384, grid_cap);
 }
 
-void SparseGatherF32(const float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                     float* out, hipStream_t s, int key_shift, uint64_t row_base,
-                     uint64_t table_rows, int grid_cap) {
-  if (row_len % 4 == 0) {
-    hipLaunchKernelGGL(gather_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
-                       dim3(kBlock), 0, s, reinterpret_cast<const float4*>(table), rows_dev,
-                       nrows, row_len / 4, reinterpret_cast<float4*>(out), key_shift, row_base,
-                       table_rows);
+void SparseGatherF32(const float* table, const SparseRows& r, float* out) {
+  if (r.row_len % 4 == 0) {
+    hipLaunchKernelGGL(gather_rows_f32, dim3(SparseGrid(r.nrows * (r.row_len / 4), r.grid_cap)),
+                       dim3(kBlock), 0, r.s, reinterpret_cast<const float4*>(table), r.keys,
+                       r.nrows, r.row_len / 4, reinterpret_cast<float4*>(out), r.key_shift,
+                       r.row_base, r.table_rows);
   } else {
-    hipLaunchKernelGGL(gather_rows_scalar_f32, dim3(SparseGrid(nrows * row_len, grid_cap)),
-                       dim3(kBlock), 0, s, table, rows_dev, nrows, row_len, out, key_shift,
-                       row_base, table_rows);
+    hipLaunchKernelGGL(gather_rows_scalar_f32, dim3(SparseGrid(r.nrows * r.row_len, r.grid_cap)),
+                       dim3(kBlock), 0, r.s, table, r.keys, r.nrows, r.row_len, out, r.key_shift,
+                       r.row_base, r.table_rows);
   }
 }
 
-void SparseScatterAssignF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                            const float* src, hipStream_t s, int key_shift, uint64_t row_base,
-                            uint64_t table_rows, int grid_cap) {
-  if (row_len % 4 == 0) {
-    hipLaunchKernelGGL(scatter_assign_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
-                       dim3(kBlock), 0, s, reinterpret_cast<float4*>(table), rows_dev, nrows,
-                       row_len / 4, reinterpret_cast<const float4*>(src), key_shift, row_base,
-                       table_rows);
+void SparseScatterAssignF32(float* table, const SparseRows& r, const float* src) {
+  if (r.row_len % 4 == 0) {
+    hipLaunchKernelGGL(scatter_assign_rows_f32,
+                       dim3(SparseGrid(r.nrows * (r.row_len / 4), r.grid_cap)), dim3(kBlock), 0,
+                       r.s, reinterpret_cast<float4*>(table), r.keys, r.nrows, r.row_len / 4,
+                       reinterpret_cast<const float4*>(src), r.key_shift, r.row_base,
+                       r.table_rows);
   } else {
     hipLaunchKernelGGL(scatter_assign_rows_scalar_f32,
-                       dim3(SparseGrid(nrows * row_len, grid_cap)), dim3(kBlock), 0, s, table,
-                       rows_dev, nrows, row_len, src, key_shift, row_base, table_rows);
+                       dim3(SparseGrid(r.nrows * r.row_len, r.grid_cap)), dim3(kBlock), 0, r.s,
+                       table, r.keys, r.nrows, r.row_len, src, r.key_shift, r.row_base,
+                       r.table_rows);
   }
 }
 
-void SparseScatterAddF32(float* table, const uint64_t* rows_dev, size_t nrows, size_t row_len,
-                         const float* src, bool atomic, hipStream_t s, int key_shift,
-                         uint64_t row_base, uint64_t table_rows, int grid_cap) {
-  if (atomic || row_len % 4 != 0) {
-    hipLaunchKernelGGL(scatter_add_rows_atomic_f32, dim3(SparseGrid(nrows * row_len, grid_cap)),
-                       dim3(kBlock), 0, s, table, rows_dev, nrows, row_len, src, key_shift,
-                       row_base, table_rows);
+void SparseScatterAddF32(float* table, const SparseRows& r, const float* src, bool atomic) {
+  if (atomic || r.row_len % 4 != 0) {
+    hipLaunchKernelGGL(scatter_add_rows_atomic_f32,
+                       dim3(SparseGrid(r.nrows * r.row_len, r.grid_cap)), dim3(kBlock), 0, r.s,
+                       table, r.keys, r.nrows, r.row_len, src, r.key_shift, r.row_base,
+                       r.table_rows);
   } else {
-    hipLaunchKernelGGL(scatter_add_rows_f32, dim3(SparseGrid(nrows * (row_len / 4), grid_cap)),
-                       dim3(kBlock), 0, s, reinterpret_cast<float4*>(table), rows_dev, nrows,
-                       row_len / 4, reinterpret_cast<const float4*>(src), key_shift, row_base,
-                       table_rows);
+    hipLaunchKernelGGL(scatter_add_rows_f32,
+                       dim3(SparseGrid(r.nrows * (r.row_len / 4), r.grid_cap)), dim3(kBlock), 0,
+                       r.s, reinterpret_cast<float4*>(table), r.keys, r.nrows, r.row_len / 4,
+                       reinterpret_cast<const float4*>(src), r.key_shift, r.row_base,
+                       r.table_rows);
   }
 }
 

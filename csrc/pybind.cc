@@ -35,6 +35,119 @@ kern::Bf16Rounding ParseRounding(const std::string& name) {
   throw py::value_error("rounding must be \"stochastic\" or \"nearest\" (got \"" + name + "\")");
 }
 
+// The k_sparse_* bindings. What a table takes beside its pointer differs by
+// binding: nothing (gather, assign, every fp32 step), `atomic` (the fp32 add)
+// or `rounding, seed` (a bf16 table's add and steps). Extra is that part of a
+// binding's signature, TableOf reads it, and `extra` names it to Python.
+struct SparseTableArg {
+  kern::SparseTable table;
+  bool atomic = false;
+};
+SparseTableArg TableOf(kern::SparseDtype dtype, uintptr_t p) {
+  return {{reinterpret_cast<void*>(p), dtype}};
+}
+SparseTableArg TableOf(kern::SparseDtype dtype, uintptr_t p, bool atomic) {
+  return {{reinterpret_cast<void*>(p), dtype}, atomic};
+}
+SparseTableArg TableOf(kern::SparseDtype dtype, uintptr_t p, const std::string& rounding,
+                       uint64_t seed) {
+  return {{reinterpret_cast<void*>(p), dtype, ParseRounding(rounding), seed}};
+}
+kern::SparseRows RowsOf(uintptr_t rows, size_t nrows, size_t row_len, int key_shift,
+                        uint64_t row_base, uint64_t table_rows, int grid_cap) {
+  return {reinterpret_cast<const uint64_t*>(rows), nrows, row_len, key_shift, row_base,
+          table_rows, nullptr, grid_cap};
+}
+kern::SparseWire WireOf(kern::SparseDtype dtype, uintptr_t p) {
+  return {reinterpret_cast<void*>(p), dtype};
+}
+
+enum class SparseMove { kGather, kAssign, kAdd };
+
+// gather, assign and add: (table, rows, nrows, row_len, out | src, Extra...,
+// key_shift, row_base, table_rows, grid_cap)
+template <class... Extra, class... Args>
+void DefSparseMove(py::module_& m, const std::string& name, SparseMove op, kern::SparseDtype tab,
+                   kern::SparseDtype wire, const char* wire_name, Args... extra) {
+  m.def(
+      name.c_str(),
+      [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t f, Extra... x,
+          int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+        SparseTableArg t = TableOf(tab, table, x...);
+        kern::SparseRows r =
+            RowsOf(rows, nrows, row_len, key_shift, row_base, table_rows, grid_cap);
+        if (op == SparseMove::kGather) {
+          kern::SparseGather(t.table, r, WireOf(wire, f));
+        } else if (op == SparseMove::kAssign) {
+          kern::SparseScatterAssign(t.table, r, WireOf(wire, f));
+        } else {
+          kern::SparseScatterAdd(t.table, r, WireOf(wire, f), t.atomic);
+        }
+        gpu::DeviceSync(-1);
+      },
+      py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg(wire_name),
+      extra..., py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+      py::arg("grid_cap") = 0);
+}
+
+// the steps: (table, state, rows, nrows, row_len, grad, out, lr, [beta1,
+// beta2,] eps, rowwise, Extra..., key_shift, row_base, table_rows, grid_cap)
+template <class... Extra, class... Args>
+void DefSparseSteps(py::module_& m, const std::string& suffix, kern::SparseDtype tab,
+                    kern::SparseDtype wire, Args... extra) {
+  m.def(
+      ("k_sparse_adagrad" + suffix).c_str(),
+      [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+          uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise, Extra... x,
+          int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
+        kern::SparseAdagrad(
+            TableOf(tab, table, x...).table, reinterpret_cast<float*>(state),
+            RowsOf(rows, nrows, row_len, key_shift, row_base, table_rows, grid_cap),
+            WireOf(wire, grad), WireOf(wire, out), {lr, eps, rowwise});
+        gpu::DeviceSync(-1);
+      },
+      py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+      py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"), extra...,
+      py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
+      py::arg("grid_cap") = 0);
+  m.def(
+      ("k_sparse_lazy_adam" + suffix).c_str(),
+      [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
+          uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
+          bool rowwise, Extra... x, int key_shift, uint64_t row_base, uint64_t table_rows,
+          int grid_cap) {
+        kern::SparseLazyAdam(
+            TableOf(tab, table, x...).table, reinterpret_cast<float*>(state),
+            RowsOf(rows, nrows, row_len, key_shift, row_base, table_rows, grid_cap),
+            WireOf(wire, grad), WireOf(wire, out), {lr, beta1, beta2, eps, rowwise});
+        gpu::DeviceSync(-1);
+      },
+      py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
+      py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+      py::arg("eps"), py::arg("rowwise"), extra..., py::arg("key_shift") = 0,
+      py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+}
+
+// the five bindings of one table and wire dtype
+void DefSparse(py::module_& m, const std::string& suffix, kern::SparseDtype tab,
+               kern::SparseDtype wire) {
+  DefSparseMove<>(m, "k_sparse_gather" + suffix, SparseMove::kGather, tab, wire, "out");
+  DefSparseMove<>(m, "k_sparse_scatter_assign" + suffix, SparseMove::kAssign, tab, wire, "src");
+  if (tab == kern::SparseDtype::kF32) {
+    DefSparseMove<bool>(m, "k_sparse_scatter_add" + suffix, SparseMove::kAdd, tab, wire, "src",
+                        py::arg("atomic"));
+    DefSparseSteps<>(m, suffix, tab, wire);
+  } else {
+    DefSparseMove<const std::string&, uint64_t>(m, "k_sparse_scatter_add" + suffix,
+                                                SparseMove::kAdd, tab, wire, "src",
+                                                py::arg("rounding") = "stochastic",
+                                                py::arg("seed") = 0);
+    DefSparseSteps<const std::string&, uint64_t>(m, suffix, tab, wire,
+                                                 py::arg("rounding") = "stochastic",
+                                                 py::arg("seed") = 0);
+  }
+}
+
 struct PoolBuffer {
   SArray<char> arr;
   uintptr_t ptr() const { return reinterpret_cast<uintptr_t>(arr.data()); }
@@ -1161,220 +1274,16 @@ PYBIND11_MODULE(_core, m) {
           return launches;
         },
         py::arg("segs"), py::arg("alpha") = 1.0f, py::arg("tile_cap") = 0);
-  m.def("k_sparse_gather_f32",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
-           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseGatherF32(reinterpret_cast<float*>(table),
-                                reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                reinterpret_cast<float*>(out), nullptr, key_shift, row_base,
-                                table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_add_f32",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-           bool atomic, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAddF32(reinterpret_cast<float*>(table),
-                                    reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                    reinterpret_cast<float*>(src), atomic, nullptr, key_shift,
-                                    row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("atomic"), py::arg("key_shift") = 0, py::arg("row_base") = 0,
-        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_assign_f32",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAssignF32(reinterpret_cast<float*>(table),
-                                       reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                       reinterpret_cast<float*>(src), nullptr, key_shift,
-                                       row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  // one Adagrad step over the rows (kernels.h); out = 0: no gather. lr or
-  // eps <= 0 raises ValueError before any GPU call.
-  m.def("k_sparse_adagrad_f32",
-        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-           uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise, int key_shift,
-           uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseAdagradF32(reinterpret_cast<float*>(table), reinterpret_cast<float*>(state),
-                                 reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                 reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out), lr,
-                                 eps, rowwise, nullptr, key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  // one lazy Adam step over the rows (kernels.h); out = 0: no gather. lr or
-  // eps <= 0, a beta outside [0, 1) or a state off a 16 B boundary raises
-  // ValueError before any GPU call.
-  m.def("k_sparse_lazy_adam_f32",
-        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-           uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
-           bool rowwise, int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseLazyAdamF32(reinterpret_cast<float*>(table), reinterpret_cast<float*>(state),
-                                  reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                  reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out), lr,
-                                  beta1, beta2, eps, rowwise, nullptr, key_shift, row_base,
-                                  table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
-        py::arg("eps"), py::arg("rowwise"), py::arg("key_shift") = 0, py::arg("row_base") = 0,
-        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
+  // The sparse kernels (kernels.h), one binding per operation, table dtype
+  // and wire dtype: k_sparse_<op>_f32, _bf16 (bf16 table, fp32 wire) and
+  // _bf16_wire (bf16 bits on the wire side too). The bf16 tables' adds and
+  // steps take rounding ("stochastic" or "nearest") and seed; a bad argument
+  // raises ValueError before any GPU call. out = 0: no gather.
+  DefSparse(m, "_f32", kern::SparseDtype::kF32, kern::SparseDtype::kF32);
+  DefSparse(m, "_bf16", kern::SparseDtype::kBf16, kern::SparseDtype::kF32);
+  DefSparse(m, "_bf16_wire", kern::SparseDtype::kBf16, kern::SparseDtype::kBf16);
   m.def("sparse_lazy_adam_state_floats", &kern::SparseLazyAdamStateFloats, py::arg("rows"),
         py::arg("row_len"), py::arg("rowwise"));
-  // the same ops over a bf16 table (kernels.h): table holds bf16 bits, the
-  // rest stays fp32; rounding "stochastic" or "nearest", anything else raises
-  // ValueError before any GPU call, like the siblings' argument checks
-  m.def("k_sparse_gather_bf16",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
-           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseGatherBf16(reinterpret_cast<uint16_t*>(table),
-                                 reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                 reinterpret_cast<float*>(out), nullptr, key_shift, row_base,
-                                 table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_assign_bf16",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-           int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAssignBf16(reinterpret_cast<uint16_t*>(table),
-                                        reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                        reinterpret_cast<float*>(src), nullptr, key_shift,
-                                        row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_add_bf16",
-        [](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-           const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
-           uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAddBf16(reinterpret_cast<uint16_t*>(table),
-                                     reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                     reinterpret_cast<float*>(src), ParseRounding(rounding), seed,
-                                     nullptr, key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
-        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  m.def("k_sparse_adagrad_bf16",
-        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-           uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise,
-           const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
-           uint64_t table_rows, int grid_cap) {
-          kern::SparseAdagradBf16(reinterpret_cast<uint16_t*>(table),
-                                  reinterpret_cast<float*>(state),
-                                  reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                  reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out),
-                                  lr, eps, rowwise, ParseRounding(rounding), seed, nullptr,
-                                  key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
-        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
-        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  m.def("k_sparse_lazy_adam_bf16",
-        [](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-           uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
-           bool rowwise, const std::string& rounding, uint64_t seed, int key_shift,
-           uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseLazyAdamBf16(reinterpret_cast<uint16_t*>(table),
-                                   reinterpret_cast<float*>(state),
-                                   reinterpret_cast<uint64_t*>(rows), nrows, row_len,
-                                   reinterpret_cast<float*>(grad), reinterpret_cast<float*>(out),
-                                   lr, beta1, beta2, eps, rowwise, ParseRounding(rounding), seed,
-                                   nullptr, key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
-        py::arg("eps"), py::arg("rowwise"), py::arg("rounding") = "stochastic",
-        py::arg("seed") = 0, py::arg("key_shift") = 0, py::arg("row_base") = 0,
-        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  // and with bf16 bits on the wire side too: out, src and grad hold bf16
-  // bits, the argument lists are the siblings'
-  auto u16 = [](uintptr_t p) { return reinterpret_cast<uint16_t*>(p); };
-  auto u64 = [](uintptr_t p) { return reinterpret_cast<uint64_t*>(p); };
-  m.def("k_sparse_gather_bf16_wire",
-        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t out,
-            int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseGatherBf16Wire(u16(table), u64(rows), nrows, row_len, u16(out), nullptr,
-                                     key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("out"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_assign_bf16_wire",
-        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-            int key_shift, uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAssignBf16Wire(u16(table), u64(rows), nrows, row_len, u16(src),
-                                            nullptr, key_shift, row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("key_shift") = 0, py::arg("row_base") = 0, py::arg("table_rows") = ~0ull,
-        py::arg("grid_cap") = 0);
-  m.def("k_sparse_scatter_add_bf16_wire",
-        [=](uintptr_t table, uintptr_t rows, size_t nrows, size_t row_len, uintptr_t src,
-            const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
-            uint64_t table_rows, int grid_cap) {
-          kern::SparseScatterAddBf16Wire(u16(table), u64(rows), nrows, row_len, u16(src),
-                                         ParseRounding(rounding), seed, nullptr, key_shift,
-                                         row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"), py::arg("src"),
-        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
-        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  m.def("k_sparse_adagrad_bf16_wire",
-        [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-            uintptr_t grad, uintptr_t out, float lr, float eps, bool rowwise,
-            const std::string& rounding, uint64_t seed, int key_shift, uint64_t row_base,
-            uint64_t table_rows, int grid_cap) {
-          kern::SparseAdagradBf16Wire(u16(table), reinterpret_cast<float*>(state), u64(rows),
-                                      nrows, row_len, u16(grad), u16(out), lr, eps, rowwise,
-                                      ParseRounding(rounding), seed, nullptr, key_shift, row_base,
-                                      table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("eps"), py::arg("rowwise"),
-        py::arg("rounding") = "stochastic", py::arg("seed") = 0, py::arg("key_shift") = 0,
-        py::arg("row_base") = 0, py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
-  m.def("k_sparse_lazy_adam_bf16_wire",
-        [=](uintptr_t table, uintptr_t state, uintptr_t rows, size_t nrows, size_t row_len,
-            uintptr_t grad, uintptr_t out, float lr, float beta1, float beta2, float eps,
-            bool rowwise, const std::string& rounding, uint64_t seed, int key_shift,
-            uint64_t row_base, uint64_t table_rows, int grid_cap) {
-          kern::SparseLazyAdamBf16Wire(u16(table), reinterpret_cast<float*>(state), u64(rows),
-                                       nrows, row_len, u16(grad), u16(out), lr, beta1, beta2, eps,
-                                       rowwise, ParseRounding(rounding), seed, nullptr, key_shift,
-                                       row_base, table_rows, grid_cap);
-          gpu::DeviceSync(-1);
-        },
-        py::arg("table"), py::arg("state"), py::arg("rows"), py::arg("nrows"), py::arg("row_len"),
-        py::arg("grad"), py::arg("out"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
-        py::arg("eps"), py::arg("rowwise"), py::arg("rounding") = "stochastic",
-        py::arg("seed") = 0, py::arg("key_shift") = 0, py::arg("row_base") = 0,
-        py::arg("table_rows") = ~0ull, py::arg("grid_cap") = 0);
   // ids -> sorted unique keys, summed rows, slot per occurrence (kernels.h);
   // returns the number of unique keys. grad = 0: no gradients, sums = 0: no
   // sums; sums_bf16: sums holds bf16 bits, each fp32 sum rounded to nearest

@@ -821,19 +821,7 @@ void GpuSparseHandler::GatherRespond(const KVMeta& req, const uint64_t* rows, si
                                      hipStream_t stream, KVServer<float>* server) {
   SArray<char> out = HbmPool::Get()->AllocArray(wire_bytes(n));
   OrderAfter(stream);
-  if (wire16()) {
-    kern::SparseGatherBf16Wire(reinterpret_cast<const uint16_t*>(table_.data()), rows, n, row_len_,
-                               reinterpret_cast<uint16_t*>(out.data()), stream, key_shift_,
-                               row_base_, rows_);
-  } else if (bf16()) {
-    kern::SparseGatherBf16(reinterpret_cast<const uint16_t*>(table_.data()), rows, n, row_len_,
-                           reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_,
-                           rows_);
-  } else {
-    kern::SparseGatherF32(reinterpret_cast<const float*>(table_.data()), rows, n, row_len_,
-                          reinterpret_cast<float*>(out.data()), stream, key_shift_, row_base_,
-                          rows_);
-  }
+  kern::SparseGather(Table(/*rounds=*/false), Rows(rows, n, stream), Wire(out.data()));
   Publish(stream);
   RespondRows(req, out, n, stream, server);
 }
@@ -842,10 +830,6 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
                                      const uint64_t* rows, hipStream_t stream,
                                      KVServer<float>* server) {
   size_t n = kvs.keys.size();
-  float* table = reinterpret_cast<float*>(table_.data());
-  uint16_t* table16 = reinterpret_cast<uint16_t*>(table_.data());
-  // a bf16 wire: the pushed floats are pairs of bf16 bits
-  const uint16_t* vals16 = reinterpret_cast<const uint16_t*>(kvs.vals.data());
   XPS_CHECK(req.cmd == kCmdDefault || req.cmd == kCmdAssign || req.cmd == kCmdSum)
       << "optimizer sparse handler: cmd " << req.cmd << " names no operation";
   if (req.cmd == kCmdDefault) {
@@ -854,33 +838,16 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     SArray<char> out;
     if (req.pull) out = HbmPool::Get()->AllocArray(wire_bytes(n));
     OrderAfter(stream);
-    float* out_rows = req.pull ? reinterpret_cast<float*>(out.data()) : nullptr;
-    uint16_t* out16 = reinterpret_cast<uint16_t*>(out_rows);
     float* state = reinterpret_cast<float*>(state_.data());
     float lr = lr_.load(std::memory_order_relaxed);
-    if (wire16() && lazy_adam()) {
-      kern::SparseLazyAdamBf16Wire(table16, state, rows, n, row_len_, vals16, out16, lr, opt_.beta1,
-                                   opt_.beta2, opt_.eps, rowwise(), opt_.rounding, NextSeed(),
-                                   stream, key_shift_, row_base_, rows_);
-    } else if (wire16()) {
-      kern::SparseAdagradBf16Wire(table16, state, rows, n, row_len_, vals16, out16, lr, opt_.eps,
-                                  rowwise(), opt_.rounding, NextSeed(), stream, key_shift_,
-                                  row_base_, rows_);
-    } else if (bf16() && lazy_adam()) {
-      kern::SparseLazyAdamBf16(table16, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
-                               opt_.beta1, opt_.beta2, opt_.eps, rowwise(), opt_.rounding,
-                               NextSeed(), stream, key_shift_, row_base_, rows_);
-    } else if (bf16()) {
-      kern::SparseAdagradBf16(table16, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
-                              opt_.eps, rowwise(), opt_.rounding, NextSeed(), stream, key_shift_,
-                              row_base_, rows_);
-    } else if (lazy_adam()) {
-      kern::SparseLazyAdamF32(table, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
-                              opt_.beta1, opt_.beta2, opt_.eps, rowwise(), stream, key_shift_,
-                              row_base_, rows_);
+    kern::SparseWire out_rows = Wire(req.pull ? out.data() : nullptr);
+    if (lazy_adam()) {
+      kern::SparseLazyAdam(Table(/*rounds=*/true), state, Rows(rows, n, stream),
+                           Wire(kvs.vals.data()), out_rows,
+                           {lr, opt_.beta1, opt_.beta2, opt_.eps, rowwise()});
     } else {
-      kern::SparseAdagradF32(table, state, rows, n, row_len_, kvs.vals.data(), out_rows, lr,
-                             opt_.eps, rowwise(), stream, key_shift_, row_base_, rows_);
+      kern::SparseAdagrad(Table(/*rounds=*/true), state, Rows(rows, n, stream),
+                          Wire(kvs.vals.data()), out_rows, {lr, opt_.eps, rowwise()});
     }
     Publish(stream);
     if (req.pull) {
@@ -889,24 +856,12 @@ void GpuSparseHandler::OptimizerPush(const KVMeta& req, const KVPairs<float>& kv
     }
   } else {
     OrderAfter(stream);
-    if (wire16() && req.cmd == kCmdSum) {
-      kern::SparseScatterAddBf16Wire(table16, rows, n, row_len_, vals16, opt_.rounding, NextSeed(),
-                                     stream, key_shift_, row_base_, rows_);
-    } else if (wire16()) {
-      kern::SparseScatterAssignBf16Wire(table16, rows, n, row_len_, vals16, stream, key_shift_,
-                                        row_base_, rows_);
-    } else if (bf16() && req.cmd == kCmdSum) {
-      kern::SparseScatterAddBf16(table16, rows, n, row_len_, kvs.vals.data(), opt_.rounding,
-                                 NextSeed(), stream, key_shift_, row_base_, rows_);
-    } else if (bf16()) {
-      kern::SparseScatterAssignBf16(table16, rows, n, row_len_, kvs.vals.data(), stream,
-                                    key_shift_, row_base_, rows_);
-    } else if (req.cmd == kCmdSum) {
-      kern::SparseScatterAddF32(table, rows, n, row_len_, kvs.vals.data(), /*atomic=*/false, stream,
-                                key_shift_, row_base_, rows_);
+    if (req.cmd == kCmdSum) {
+      kern::SparseScatterAdd(Table(/*rounds=*/true), Rows(rows, n, stream),
+                             Wire(kvs.vals.data()));
     } else {
-      kern::SparseScatterAssignF32(table, rows, n, row_len_, kvs.vals.data(), stream, key_shift_,
-                                   row_base_, rows_);
+      kern::SparseScatterAssign(Table(/*rounds=*/false), Rows(rows, n, stream),
+                                Wire(kvs.vals.data()));
     }
     Publish(stream);
     if (req.pull) {
@@ -924,7 +879,6 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
   hipStream_t stream = Stream(req.sender);
   size_t n = kvs.keys.size();
   XPS_CHECK_GT(n, 0u);
-  float* table = reinterpret_cast<float*>(table_.data());
   if (req.push) {
     XPS_CHECK(kvs.vals.on_device()) << "sparse push needs device vals (pool buffers)";
     XPS_CHECK_EQ(kvs.vals.size(), wire_bytes(n) / sizeof(float));
@@ -934,11 +888,11 @@ void GpuSparseHandler::operator()(const KVMeta& req, const KVPairs<float>& kvs,
       return;
     }
     if (accumulate_ || req.cmd == kCmdSum) {
-      kern::SparseScatterAddF32(table, rows, n, row_len_, kvs.vals.data(), atomic_,
-                                stream, key_shift_, row_base_, rows_);
+      kern::SparseScatterAdd(Table(/*rounds=*/false), Rows(rows, n, stream),
+                             Wire(kvs.vals.data()), atomic_);
     } else {
-      kern::SparseScatterAssignF32(table, rows, n, row_len_, kvs.vals.data(), stream, key_shift_,
-                                   row_base_, rows_);
+      kern::SparseScatterAssign(Table(/*rounds=*/false), Rows(rows, n, stream),
+                                Wire(kvs.vals.data()));
     }
     if (req.pull) {
       // fused round (ZPushPull): gather the post-scatter rows on the

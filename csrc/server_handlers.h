@@ -170,7 +170,7 @@ class GpuDenseHandler {
 //
 // With an optimizer the handler keeps the optimizer state beside the table
 // and the push's cmd names the operation: kCmdDefault = one gradient step
-// (kern::SparseAdagradF32 or kern::SparseLazyAdamF32; state updated),
+// (kern::SparseAdagrad or kern::SparseLazyAdam; state updated),
 // kCmdAssign = assign rows (how weights are initialised; state untouched),
 // kCmdSum = add (state untouched). `accumulate` plays no part then.
 //
@@ -178,7 +178,7 @@ class GpuDenseHandler {
 // rows * row_len * 2 bytes and goes through kern::Sparse*Bf16. By default
 // the wire does not change: pushes and pull responses stay fp32. With
 // wire_dtype kBf16 (needs a bf16 table and an even row_len) every pushed
-// value and every pulled row is bf16 bits, through kern::Sparse*Bf16Wire:
+// value and every pulled row is bf16 bits, through a bf16 kern::SparseWire:
 // a row is row_len / 2 of the floats that lens and vals.size() count, a pull
 // is exact, and a step leaves the bits the fp32 wire leaves for the same
 // gradient values. Nothing of it is checkpointed. The
@@ -215,7 +215,7 @@ class GpuSparseHandler {
   void operator()(const KVMeta& req, const KVPairs<float>& kvs, KVServer<float>* server);
   uintptr_t table_ptr() const { return reinterpret_cast<uintptr_t>(table_.data()); }
   // the optimizer state; 0 without one. Adagrad: rows floats row-wise, else
-  // the table's shape. Lazy Adam: kern::SparseLazyAdamF32's records.
+  // the table's shape. Lazy Adam: kern::SparseLazyAdam's records.
   uintptr_t state_ptr() const { return reinterpret_cast<uintptr_t>(state_.data()); }
   // learning rate of the gradient steps handled after the call
   void set_lr(float lr) { lr_.store(lr, std::memory_order_relaxed); }
@@ -266,6 +266,19 @@ class GpuSparseHandler {
   }
   // the seed of the next launch that rounds; counts it
   uint64_t NextSeed() { return kern::SparseBf16LaunchSeed(opt_.seed, launches_.fetch_add(1)); }
+  // The kernels' description of a call (kernels.h): our table, n message rows
+  // on a stream, wire rows at p. rounds: the launch rounds on the store (an
+  // add, a step), so on a bf16 table it takes the next seed.
+  kern::SparseTable Table(bool rounds) {
+    if (!bf16()) return {table_.data(), kern::SparseDtype::kF32};
+    return {table_.data(), kern::SparseDtype::kBf16, opt_.rounding, rounds ? NextSeed() : 0};
+  }
+  kern::SparseRows Rows(const uint64_t* keys, size_t n, hipStream_t s) const {
+    return {keys, n, row_len_, key_shift_, row_base_, rows_, s};
+  }
+  kern::SparseWire Wire(const void* p) const {
+    return {const_cast<void*>(p), wire16() ? kern::SparseDtype::kBf16 : kern::SparseDtype::kF32};
+  }
 
   Postoffice* po_;
   size_t rows_;

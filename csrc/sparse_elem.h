@@ -1,7 +1,7 @@
-// The per-element arithmetic of the sparse optimizer steps, stated once for
-// the fp32 kernels (sparse_opt.hip) and the bf16-table kernels
-// (sparse_bf16.hip): both files compile these with unpaired fp32 operations,
-// so a step computes the same fp32 value whatever the table stores.
+// The per-element arithmetic of the sparse optimizer steps (sparse_table.hip),
+// stated once for every table and wire and compiled with unpaired fp32
+// operations, so a step computes the same fp32 value whatever the table
+// stores.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,7 +18,7 @@ __device__ inline float Denom(float s, float eps) { return sqrtf(s) + eps; }
 
 // Lazy Adam. beta * old + omb * x: both moments, the row-wise second one
 // included. Two rounded products and their rounded sum: left to the compiler,
-// either product may be fused into the add, and the two files' kernels chose
+// either product may be fused into the add, and two kernels have chosen
 // differently (a last-bit difference in m' and v'), so contraction is off here
 __device__ inline float Moment(float old, float x, float beta, float omb) {
 #pragma clang fp contract(off)

@@ -1,8 +1,7 @@
-// One-process timing of the fused Adagrad step (csrc/sparse_opt.hip)
+// One-process timing of the fused Adagrad step (csrc/sparse_table.hip)
 // against the launches it replaces in a fused sparse round, the
 // scatter-add and the gather of csrc/kernels.hip, on the same buffers.
-// Links kernels.hip, sparse_opt.hip and sparse_bf16.hip only: no cluster, no
-// Python.
+// Links kernels.hip and sparse_table.hip only: no cluster, no Python.
 //
 //   build/bench_sparse_adagrad [--rounds N] [--opt lazy_adam|rowwise_lazy_adam] [--bf16]
 //                              [--row-len L]
@@ -13,17 +12,17 @@
 // disjoint sets of 8192 rows taken in turn (128 MiB of table rows between
 // two visits of a set). Every round times, each between its own pair of
 // HIP events and in alternation:
-//   fused   SparseAdagradF32, row-wise, with out  (one launch)
-//   pair    SparseScatterAddF32 + SparseGatherF32 (two launches)
+//   fused   SparseAdagrad, row-wise, with out     (one launch)
+//   pair    SparseScatterAdd + SparseGather       (two launches)
 // With --opt the rounds time instead, in the same alternation:
-//   adam    SparseLazyAdamF32 of that variant, with out (one launch)
-//   adagrad SparseAdagradF32, row-wise, with out        (one launch)
+//   adam    SparseLazyAdam of that variant, with out (one launch)
+//   adagrad SparseAdagrad, row-wise, with out        (one launch)
 // With --bf16 the rounds time three pairs, the bf16-table kernel
-// (sparse_bf16.hip, stochastic rounding) beside its fp32 sibling on the same
+// (stochastic rounding) beside its fp32 sibling on the same
 // keys, gradients, state and out, the sibling's set half a turn away:
 //   adagrad / adagrad16   row-wise Adagrad step with out
 //   adam / adam16         row-wise lazy Adam step with out
-//   gather / gather16     SparseGatherF32 / SparseGatherBf16
+//   gather / gather16     SparseGather over the fp32 / the bf16 table
 // and after each bf16-table kernel its 16-bit-wire sibling (adagrad16w,
 // adam16w, gather16w: bf16 gradient in, bf16 rows out) on the same keys.
 // Output: median, 10th and 90th percentile of each in microseconds.
@@ -75,6 +74,21 @@ __global__ void fresh_kernel(float* p, size_t n, size_t rec) {
   for (; i < n; i += stride) p[i] = i % rec < 2 ? 1.f : 0.f;
 }
 
+namespace k = xps::kern;
+
+// the calls' descriptions: kHot rows at keys, an fp32 or a bf16 array
+k::SparseRows Rows(const uint64_t* keys, size_t nrows = kHot) {
+  return {keys, nrows, g_row_len, 0, 0, kRows};
+}
+k::SparseTable F32(float* p) { return {p, k::SparseDtype::kF32}; }
+k::SparseTable Bf16(uint16_t* p, uint64_t seed) {
+  return {p, k::SparseDtype::kBf16, k::Bf16Rounding::kStochastic, seed};
+}
+k::SparseWire Wire(float* p) { return {p, k::SparseDtype::kF32}; }
+k::SparseWire Wire(uint16_t* p) { return {p, k::SparseDtype::kBf16}; }
+const k::AdagradParams kAdagrad{0.01f, 1e-8f, /*rowwise=*/true};
+k::LazyAdamParams Adam(bool rowwise) { return {0.01f, 0.9f, 0.999f, 1e-8f, rowwise}; }
+
 void Report(const char* schedule, const char* name, std::vector<float>* us) {
   std::sort(us->begin(), us->end());
   size_t n = us->size();
@@ -99,7 +113,7 @@ float TimeUs(hipEvent_t e0, hipEvent_t e1, Fn fn) {
 // turn away, as the pair does in the default mode
 void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* grad, float* out,
                 const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
-  size_t nstate = xps::kern::SparseLazyAdamStateFloats(kRows, g_row_len, rowwise);
+  size_t nstate = k::SparseLazyAdamStateFloats(kRows, g_row_len, rowwise);
   float* records;
   CHECK(hipMalloc(reinterpret_cast<void**>(&records), nstate * 4));
   hipLaunchKernelGGL(fresh_kernel, dim3(4096), dim3(256), 0, nullptr, records, nstate,
@@ -111,14 +125,12 @@ void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* gra
       size_t turn = static_cast<size_t>(r + 20);
       const uint64_t* k = keys + (rotating ? (turn % kSets) * kHot : 0);
       float us = TimeUs(e0, e1, [&] {
-        xps::kern::SparseLazyAdamF32(table, records, k, kHot, g_row_len, grad, out, 0.01f, 0.9f,
-                                     0.999f, 1e-8f, rowwise, nullptr, 0, 0, kRows);
+        k::SparseLazyAdam(F32(table), records, Rows(k), Wire(grad), Wire(out), Adam(rowwise));
       });
       if (r >= 0) us_adam.push_back(us);
       if (rotating) k = keys + ((turn + kSets / 2) % kSets) * kHot;
       us = TimeUs(e0, e1, [&] {
-        xps::kern::SparseAdagradF32(table, state, k, kHot, g_row_len, grad, out, 0.01f, 1e-8f,
-                                    /*rowwise=*/true, nullptr, 0, 0, kRows);
+        k::SparseAdagrad(F32(table), state, Rows(k), Wire(grad), Wire(out), kAdagrad);
       });
       if (r >= 0) us_adagrad.push_back(us);
     }
@@ -135,8 +147,6 @@ void AdamRounds(bool rowwise, int rounds, float* table, float* state, float* gra
 // reads. The 16-bit wire reads the gradient's upper halves and writes out16.
 void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
                 const uint64_t* keys, hipEvent_t e0, hipEvent_t e1) {
-  namespace k = xps::kern;
-  const auto kSr = k::Bf16Rounding::kStochastic;
   size_t nstate = k::SparseLazyAdamStateFloats(kRows, g_row_len, true);
   float* records;
   uint16_t *table16, *grad16, *out16;
@@ -154,7 +164,7 @@ void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
   uint64_t* all;
   CHECK(hipMalloc(reinterpret_cast<void**>(&all), kRows * 8));
   CHECK(hipMemcpy(all, h.data(), kRows * 8, hipMemcpyHostToDevice));
-  k::SparseScatterAssignBf16(table16, all, kRows, g_row_len, table, nullptr, 0, 0, kRows);
+  k::SparseScatterAssign(Bf16(table16, 0), Rows(all, kRows), Wire(table));
   CHECK(hipDeviceSynchronize());
   CHECK(hipFree(all));
   for (int rotating = 0; rotating < 2; ++rotating) {
@@ -166,37 +176,34 @@ void Bf16Rounds(int rounds, float* table, float* state, float* grad, float* out,
       uint64_t seed = turn;
       float t[9];
       t[0] = TimeUs(e0, e1, [&] {
-        k::SparseAdagradF32(table, state, kf, kHot, g_row_len, grad, out, 0.01f, 1e-8f, true,
-                            nullptr, 0, 0, kRows);
+        k::SparseAdagrad(F32(table), state, Rows(kf), Wire(grad), Wire(out), kAdagrad);
       });
       t[1] = TimeUs(e0, e1, [&] {
-        k::SparseAdagradBf16(table16, state, kb, kHot, g_row_len, grad, out, 0.01f, 1e-8f, true, kSr,
-                             seed, nullptr, 0, 0, kRows);
+        k::SparseAdagrad(Bf16(table16, seed), state, Rows(kb), Wire(grad), Wire(out), kAdagrad);
       });
       t[2] = TimeUs(e0, e1, [&] {
-        k::SparseAdagradBf16Wire(table16, state, kb, kHot, g_row_len, grad16, out16, 0.01f, 1e-8f,
-                                 true, kSr, seed, nullptr, 0, 0, kRows);
+        k::SparseAdagrad(Bf16(table16, seed), state, Rows(kb), Wire(grad16), Wire(out16),
+                         kAdagrad);
       });
       t[3] = TimeUs(e0, e1, [&] {
-        k::SparseLazyAdamF32(table, records, kf, kHot, g_row_len, grad, out, 0.01f, 0.9f, 0.999f,
-                             1e-8f, true, nullptr, 0, 0, kRows);
+        k::SparseLazyAdam(F32(table), records, Rows(kf), Wire(grad), Wire(out), Adam(true));
       });
       t[4] = TimeUs(e0, e1, [&] {
-        k::SparseLazyAdamBf16(table16, records, kb, kHot, g_row_len, grad, out, 0.01f, 0.9f, 0.999f,
-                              1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
+        k::SparseLazyAdam(Bf16(table16, seed), records, Rows(kb), Wire(grad), Wire(out),
+                          Adam(true));
       });
       t[5] = TimeUs(e0, e1, [&] {
-        k::SparseLazyAdamBf16Wire(table16, records, kb, kHot, g_row_len, grad16, out16, 0.01f, 0.9f,
-                                  0.999f, 1e-8f, true, kSr, seed, nullptr, 0, 0, kRows);
+        k::SparseLazyAdam(Bf16(table16, seed), records, Rows(kb), Wire(grad16), Wire(out16),
+                          Adam(true));
       });
       t[6] = TimeUs(e0, e1, [&] {
-        k::SparseGatherF32(table, kf, kHot, g_row_len, out, nullptr, 0, 0, kRows);
+        k::SparseGather(F32(table), Rows(kf), Wire(out));
       });
       t[7] = TimeUs(e0, e1, [&] {
-        k::SparseGatherBf16(table16, kb, kHot, g_row_len, out, nullptr, 0, 0, kRows);
+        k::SparseGather(Bf16(table16, 0), Rows(kb), Wire(out));
       });
       t[8] = TimeUs(e0, e1, [&] {
-        k::SparseGatherBf16Wire(table16, kb, kHot, g_row_len, out16, nullptr, 0, 0, kRows);
+        k::SparseGather(Bf16(table16, 0), Rows(kb), Wire(out16));
       });
       for (int i = 0; i < 9 && r >= 0; ++i) us[i].push_back(t[i]);
     }
@@ -274,8 +281,7 @@ int main(int argc, char** argv) {
       const uint64_t* k = keys + (rotating ? (static_cast<size_t>(r + 20) % kSets) * kHot : 0);
       float ms = 0;
       CHECK(hipEventRecord(e0, nullptr));
-      xps::kern::SparseAdagradF32(table, state, k, kHot, g_row_len, grad, out, 0.01f, 1e-8f,
-                                  /*rowwise=*/true, nullptr, 0, 0, kRows);
+      xps::kern::SparseAdagrad(F32(table), state, Rows(k), Wire(grad), Wire(out), kAdagrad);
       CHECK(hipEventRecord(e1, nullptr));
       CHECK(hipEventSynchronize(e1));
       CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -284,9 +290,8 @@ int main(int argc, char** argv) {
       // launch found its own
       if (rotating) k = keys + (static_cast<size_t>(r + 20 + kSets / 2) % kSets) * kHot;
       CHECK(hipEventRecord(e0, nullptr));
-      xps::kern::SparseScatterAddF32(table, k, kHot, g_row_len, grad, /*atomic=*/false, nullptr, 0,
-                                     0, kRows);
-      xps::kern::SparseGatherF32(table, k, kHot, g_row_len, out, nullptr, 0, 0, kRows);
+      xps::kern::SparseScatterAdd(F32(table), Rows(k), Wire(grad));
+      xps::kern::SparseGather(F32(table), Rows(k), Wire(out));
       CHECK(hipEventRecord(e1, nullptr));
       CHECK(hipEventSynchronize(e1));
       CHECK(hipEventElapsedTime(&ms, e0, e1));

@@ -1,4 +1,4 @@
-"""Exact model of the bf16 table's store rule (the header of csrc/sparse_bf16.hip, "bf16 tables"
+"""Exact model of the bf16 table's store rule (the header of csrc/sparse_table.hip, "bf16 tables"
 in docs/API.md) in numpy and Python ints, shared by test_bf16_store_model.py and the
 test_sparse_bf16_exact*.py files. The model defines the rule; the kernels are compared with it
 bit for bit.
@@ -12,7 +12,7 @@ all in 64-bit wrap-around arithmetic. Inf and NaN skip the add; a NaN whose mant
 dropped half alone gets bit 0x40.
 
 adagrad_step and lazy_adam_step transcribe the fp32 operation order of csrc/sparse_elem.h and of
-the lazy-Adam comment in csrc/sparse_opt.hip, one numpy float32 operation per stated operation.
+the lazy-Adam comment in csrc/sparse_table.hip, one numpy float32 operation per stated operation.
 They are exact where no product that a compiler may fuse into an add is inexact; the row's sum of
 squares is taken in float64 and must be exact there too."""
 import numpy as np

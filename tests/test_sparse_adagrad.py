@@ -1,4 +1,4 @@
-"""kern::SparseAdagradF32 (csrc/sparse_opt.hip) against the update in numpy float64 from the
+"""kern::SparseAdagrad on an fp32 table (csrc/sparse_table.hip) against the update in numpy float64 from the
 same fp32 inputs. With every fp32 operation within u = 2^-23 relative and a sum of L squares
 within L*u: |w - w_ref| <= u * (|w_ref| + (L/2 + 5) * |step_ref|) and |s - s_ref| <=
 (L + 3) * u * |s_ref|, L = row_len row-wise, 1 element-wise. Table, state and out lie inside

@@ -1,4 +1,4 @@
-"""The bf16-table kernels (csrc/sparse_bf16.hip) against numpy float64 from the same inputs, on
+"""The bf16-table kernels (csrc/sparse_table.hip) against numpy float64 from the same inputs, on
 test_sparse_adagrad.py's keys and inside its guard bytes. A step's fp32 result x obeys the fp32
 tests' bound against the reference; the stored s = R(x) adds the rounding: |s - ref| <= ulp / 2 +
 bound under nearest, < ulp + bound under stochastic, ulp = 2^(floor(log2(max(|s|, |ref|))) - 7).

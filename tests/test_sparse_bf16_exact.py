@@ -1,4 +1,4 @@
-"""The bf16-table kernels (csrc/sparse_bf16.hip) against tests/bf16_store_model.py, bit for bit:
+"""The bf16-table kernels (csrc/sparse_table.hip) against tests/bf16_store_model.py, bit for bit:
 every assertion on table, state and out is an equality of bits. test_sparse_bf16.py bounds a stored
 value within an ulp; here the stored bits are the model's R(x), with the 16 random bits of every
 element computed from (seed, local table row, element index).
@@ -8,7 +8,7 @@ a step is exact on inputs no contraction can change. hipcc may fuse a * b + c, w
 the unfused form only where a * b is inexact, so the steps run on gradients k / 16 with |k| <= 64
 (squares and sums of up to 2056 of them are exact fp32), beta1 = beta2 = 1/2, p = 2^-k and bf16
 weights, with lr, eps and the state arbitrary; division and square root round correctly. On those
-inputs the fp32 kernels of sparse_opt.hip leave the same x and state bits as the model (the claim
+inputs the fp32 kernels of sparse_table.hip leave the same x and state bits as the model (the claim
 of sparse_elem.h), and on ordinary inputs the element-wise bf16 kernels leave the fp32 kernels'
 state bits and R of their x.
 

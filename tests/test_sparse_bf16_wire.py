@@ -1,4 +1,4 @@
-"""The bf16-table kernels with bf16 bits on the wire (kern::Sparse*Bf16Wire) on test_sparse_bf16.py's
+"""The bf16-table kernels with bf16 bits on the wire (kern::Sparse* with a bf16 SparseWire) on test_sparse_bf16.py's
 inputs and inside its guard bytes. Fed gradient bits b, a step leaves the table and state bits
 k_sparse_*_bf16 leaves fed widen(b), and its out is those table bits; the stored values keep that
 file's rule against float64 from the same inputs. Row lengths: 2 and 8 (one unit), 24 (G = 4, an

@@ -1,4 +1,4 @@
-"""kern::SparseLazyAdamF32 (csrc/sparse_opt.hip) against the update in numpy float64 from the
+"""kern::SparseLazyAdam on an fp32 table (csrc/sparse_table.hip) against the update in numpy float64 from the
 same fp32 inputs, on test_sparse_adagrad.py's grid of shapes and inside its guard bytes.
 
 Bounds from the operation order stated at the kernel: u = 2^-23 per fp32 operation, first
