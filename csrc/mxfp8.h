@@ -11,8 +11,15 @@
 // Scale of a block: amax = max|x|, be = exponent field of amax,
 // byte = max(be - 8, 0), and one more if amax * 2^(127-byte) > 448 (so
 // the block's largest element never saturates). Code of an element:
-// e4m3fn_rne(clamp(x * 2^(127-byte), -448, 448)). Inputs are finite with
-// |x| either 0 or in [2^-100, 2^100].
+// e4m3fn_rne(clamp(x * 2^(127-byte), -448, 448)). Finite inputs have |x|
+// either 0 or in [2^-100, 2^100].
+//
+// Non-finite values: a block that holds any NaN or infinity gets the scale
+// byte 0xFF (E8M0's NaN) and 32 codes 0x7F (e4m3fn's NaN), and decodes to
+// NaN in all 32 positions; every other block of the stream is unaffected.
+// The sum of a finish, acc + D(in), counts the same way, a finite sum that
+// overflows fp32 included. Decoding needs no case of its own: byte 0xFF
+// reads as 2^128 = +inf, and NaN * inf is NaN.
 #pragma once
 
 #include <cmath>
@@ -35,6 +42,8 @@ static const size_t kSuperScales = 16;       // scale bytes heading a superblock
 static const size_t kSuperBytes = 528;       // packed bytes per superblock (33 x 16)
 static const size_t kSuperF32Bytes = 2048;   // the same elements as fp32
 static const float kE4m3Max = 448.0f;
+static const uint32_t kNanScale = 0xffu;     // scale byte of a block with a NaN or an infinity
+static const uint8_t kNanCode = 0x7fu;       // its 32 codes
 
 XPS_MX_HD inline size_t MxSuperblocks(size_t n) { return (n + kSuperElems - 1) / kSuperElems; }
 XPS_MX_HD inline size_t MxPackedBytes(size_t n) { return MxSuperblocks(n) * kSuperBytes; }
@@ -57,9 +66,12 @@ XPS_MX_HD inline float BitsF32(uint32_t u) {
   return c.f;
 }
 
-// E8M0 byte of a block whose largest magnitude is amax (>= 0)
+// E8M0 byte of a block whose largest magnitude is amax (>= 0); kNanScale
+// when amax is NaN or +inf, which is how a block's maximum reports a
+// non-finite element (the maximum must propagate NaN)
 XPS_MX_HD inline uint32_t ScaleByte(float amax) {
   uint32_t be = (F32Bits(amax) >> 23) & 0xffu;
+  if (be == 0xffu) return kNanScale;
   uint32_t byte = be > 8 ? be - 8 : 0;
   // 2^(127-byte): exponent field 254 - byte, in [6, 254] for every byte
   if (amax * BitsF32((254u - byte) << 23) > kE4m3Max) ++byte;
@@ -103,15 +115,21 @@ inline void MxQuantizeHost(const float* src, size_t n, uint8_t* packed) {
     for (size_t b = 0; b < kSuperScales; ++b) {
       size_t base = sb * kSuperElems + b * kBlockElems;
       float x[kBlockElems];
-      float amax = 0.0f;
+      // the maximum of the magnitudes' bits: NaN above inf above every
+      // finite value, so a non-finite element is never dropped
+      uint32_t amax_bits = 0;
       for (size_t i = 0; i < kBlockElems; ++i) {
         x[i] = base + i < n ? src[base + i] : 0.0f;
-        float a = std::fabs(x[i]);
-        if (a > amax) amax = a;
+        uint32_t a = F32Bits(x[i]) & 0x7fffffffu;
+        if (a > amax_bits) amax_bits = a;
       }
-      uint32_t byte = ScaleByte(amax);
-      float inv = InvScale(byte);
+      uint32_t byte = ScaleByte(BitsF32(amax_bits));
       scales[b] = static_cast<uint8_t>(byte);
+      if (byte == kNanScale) {
+        std::memset(codes + b * kBlockElems, kNanCode, kBlockElems);
+        continue;
+      }
+      float inv = InvScale(byte);
       for (size_t i = 0; i < kBlockElems; ++i) {
         codes[b * kBlockElems + i] = E4m3Encode(Clamp448(x[i] * inv));
       }

@@ -17,7 +17,10 @@
 //
 // fp32 <-> e4m3 goes through v_cvt_pk_fp8_f32 / v_cvt_pk_f32_fp8 (OCP
 // e4m3fn on this target). Values are clamped to +-448 first, so the
-// instruction's overflow mode never matters.
+// instruction's overflow mode never matters. (The clamp is the format's
+// rule as written; with a finite amax the scale rule alone keeps every
+// scaled value within +-448, so no finite input can tell it is there, and
+// a non-finite block's codes are replaced, see Quant16.)
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
@@ -77,12 +80,15 @@ __device__ inline float Clamp448(float x) { return fminf(fmaxf(x, -448.0f), 448.
 
 // Quantize this lane's half block: the block's amax is the larger of this
 // lane's and its neighbour's (lane ^ 1). Returns the 16 codes; *byte is the
-// block's scale byte (the same in both lanes of the pair).
+// block's scale byte (the same in both lanes of the pair). The maximum
+// propagates NaN (v_maximum3_f32, where fmaxf would drop it), so a NaN or
+// an infinity anywhere in the block reaches ScaleByte, which answers
+// kNanScale, and the whole block becomes kNanCode (mxfp8.h).
 __device__ inline uint4 Quant16(const float (&v)[kLaneElems], uint32_t* byte) {
   float amax = 0.0f;
 #pragma unroll
-  for (int i = 0; i < kLaneElems; ++i) amax = fmaxf(amax, fabsf(v[i]));
-  amax = fmaxf(amax, __shfl_xor(amax, 1));
+  for (int i = 0; i < kLaneElems; ++i) amax = __builtin_elementwise_maximum(amax, fabsf(v[i]));
+  amax = __builtin_elementwise_maximum(amax, __shfl_xor(amax, 1));
   uint32_t b = mx::ScaleByte(amax);
   float inv = mx::InvScale(b);
   uint32_t w[4];
@@ -96,6 +102,10 @@ __device__ inline uint4 Quant16(const float (&v)[kLaneElems], uint32_t* byte) {
     w[j] = static_cast<uint32_t>(r);
   }
   *byte = b;
+  if (b == mx::kNanScale) {
+    const uint32_t nan4 = mx::kNanCode * 0x01010101u;
+    return uint4{nan4, nan4, nan4, nan4};
+  }
   return uint4{w[0], w[1], w[2], w[3]};
 }
 
